@@ -9,13 +9,25 @@ The step outputs land in a [128, N] slab that the HIP episode fold
 (`invsim_episode_fold_groups`) reduces to episodic-return statistics every
 128 steps inside the timed region (rollouts fold inside their kernels instead:
 the episode sink, `invsim_set_episode_sink`); one all-reduce of the statistics
-follows the region.  After the step region the same handle runs a timed region
-of fused K=30 rollouts (`invsim_rollout`), reported under "rollout" in the
-same line, and the step loop again as HIP-graph replays (one episode cycle per
-replay), under "graph".  The default line then times BASELINE configs 2, 4
-(per-GPU shard) and 5 the same way, under "configs".
+follows the region.  A plain run stops there: set up, warm up, time the steps,
+print the line (with the roofline fields of that region, which cost no run of
+their own).
+
+--full adds everything else the benchmark measures, in the same line: after
+the step region the same handle runs a timed region of fused K=30 rollouts
+(`invsim_rollout`), reported under "rollout", and the step loop again as
+HIP-graph replays (one episode cycle per replay), under "graph"; the default
+workload then times BASELINE configs 2, 4 (per-GPU shard) and 5 the same way,
+under "configs"; and the C oracle is timed on the host, under "cpu_baseline".
+The --no-* switches drop single parts of a --full run.
+
+--dump-outputs DIR writes what the last timed call of the headline region
+returned to its caller (obs, reward, terminated, truncated; the metric sums
+too in policy mode) as DIR/<name>.npy in float64, rank 0's shard.  The inputs
+are seeded, so two runs with the same arguments dump the same arrays.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode step|rollout]
+                  [--full] [--dump-outputs DIR]
 
 Multi-GPU (one process per GPU): under torch.distributed.run the ranks come
 from the environment (WORLD_SIZE must equal --gpus); `bench.py --gpus N` run
@@ -89,6 +101,13 @@ def parse():
     ap.add_argument("--n-envs", type=int, default=0)
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the workload's env count is the GLOBAL batch, split over ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the rollout and graph regions "
+                         "of a step run, the other BASELINE configs and the CPU baseline (each can be dropped "
+                         "again with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the headline region's last call as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the envs when they exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fold", default="auto", choices=["auto", "sink", "side", "inline", "none"],
                     help="episodic-return statistics of the timed steps: sink = folded inside the step / "
@@ -354,6 +373,7 @@ def run_region(args, env, wl, mode, steps, warmup, world, dev, gen, dist):
     end_ev = torch.cuda.Event()
     end_ev.record(stream)
     blk = [0]
+    last = [0, 0]                                   # slab and first row of the newest call's outputs
 
     def region(n_calls, timed):
         for bi in range(0, n_calls, calls_per_block):
@@ -365,6 +385,7 @@ def run_region(args, env, wl, mode, steps, warmup, world, dev, gen, dist):
                 evs[bi // calls_per_block][0].record(stream)
             for j in range(nb):
                 one(bi + j, j * rows_per_call, sl)
+            last[:] = [sl, (nb - 1) * rows_per_call]
             if timed:
                 evs[bi // calls_per_block][1].record(stream)
             rows = nb * rows_per_call
@@ -420,8 +441,39 @@ def run_region(args, env, wl, mode, steps, warmup, world, dev, gen, dist):
         B += -wl["B_act"] + 16 * metrics.shape[1] / K
     achieved = B * N * steps_per_call / (kern_ms * 1e-3) / 1e9
     achieved_wall = B * N * total_steps / el / 1e9
+    # what the last timed call handed back (views of the live buffers: [rows, N, ...], env axis 1)
+    sl, row = last
+    rows = slice(row, row + rows_per_call)
+    outputs = {"obs": obs, "reward": rew[sl, rows], "terminated": term[sl, rows], "truncated": trunc[sl, rows]}
+    if mode == "policy":
+        outputs["metrics"] = metrics.unsqueeze(0)
     return dict(el=el, calls=calls, warm=warm, steps_per_call=steps_per_call, total_steps=total_steps,
-                N=N, K=K, B=B, kern_ms=kern_ms, achieved=achieved, achieved_wall=achieved_wall, ep=ep)
+                N=N, K=K, B=B, kern_ms=kern_ms, achieved=achieved, achieved_wall=achieved_wall, ep=ep,
+                outputs=outputs)
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data per --dump-outputs (the files stay under 64 MB in all)
+
+
+def dump_outputs(path, outputs, n_envs):
+    """--dump-outputs: the last timed call's outputs ([rows, N, ...] device
+    tensors, env axis 1) as float64 `<name>.npy` files (int64 observations and
+    bool flags convert exactly).  When all envs would exceed DUMP_BUDGET the
+    same seeded sample of env indices is taken from every array and written
+    beside them as env_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    per_env = sum(8 * (t.numel() // n_envs) for t in outputs.values())
+    idx = None
+    if per_env * n_envs > DUMP_BUDGET:
+        m = max(1, DUMP_BUDGET // (per_env + 8))
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, size=m, replace=False))
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+    for name, t in outputs.items():
+        if idx is not None:
+            t = t.index_select(1, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.cpu().to(torch.float64).numpy())
 
 
 def run_graph_region(args, env, wl, steps, world, dev, gen, dist):
@@ -711,6 +763,9 @@ def main():
     gen.manual_seed(1234 + rank)
     env.reset(seed=0)
     r = run_region(args, env, wl, args.mode, args.steps, args.warmup, world, dev, gen, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"], r["N"])
+    del r["outputs"]
     full = n == wl["n"] and not args.strong and args.demand_stream == "numpy"   # the PMC files are of that run
     traffic, traffic_src = _pmc(args.workload, args.mode, full)
     N = r["N"]
@@ -747,7 +802,7 @@ def main():
             f"the timed window holds {r['total_steps']} steps, fewer than one episode cycle ({C} steps: "
             f"{C - 1} periods + the NEXT_STEP reset step), so no episode ends inside it; the rollout "
             f"region's episode_stats cover whole cycles")
-    if args.mode == "step" and not args.no_rollout_line:
+    if args.full and args.mode == "step" and not args.no_rollout_line:
         # the fused K-step rollout of the same handle, timed the same way, over a
         # whole number of episode cycles (every env finishes the same number of
         # episodes whatever the phase it starts in)
@@ -766,15 +821,15 @@ def main():
                                                 source="timed rollout batch: the episode sink in the rollout "
                                                        "kernels, or the HIP episode fold between launch "
                                                        "blocks; one all-reduce after the region")}
-    if args.mode == "step" and not args.no_graph_line and args.demand_stream == "numpy":
+    if args.full and args.mode == "step" and not args.no_graph_line and args.demand_stream == "numpy":
         out["graph"] = run_graph_region(args, env, wl, args.steps, world, dev, gen, dist)
-    if (args.mode == "step" and args.workload == "invmgmt_backlog" and not args.n_envs and not args.strong
+    if (args.full and args.mode == "step" and args.workload == "invmgmt_backlog" and not args.n_envs and not args.strong
             and args.demand_stream == "numpy" and not args.no_config_lines):
         out["configs"] = {k: config_line(args, k, world, rank, dev, dist)
                           for k in ("newsvendor", "invmgmt_lostsales", "net_backlog")}
         out["configs"]["note"] = ("BASELINE configs 2, 4 (the per-GPU shard of 262 144 envs over 8 GPUs) and 5, "
                                   "timed in this run like the headline: eager step region, then fused rollouts")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds)
         rv, rwhat = REFERENCE_PYTHON[args.workload]
         out["cpu_baseline"]["reference_python"] = {

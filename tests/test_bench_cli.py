@@ -99,6 +99,37 @@ def test_span_single_process():
     assert bench._span(1.0, 3.5, None, NoDist) == 2.5
 
 
+def test_dump_outputs_files_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float64 .npy; above the byte budget the
+    same seeded, sorted sample of envs from every array, identical from call to
+    call, with its indices beside it."""
+    import bench
+    rng = np.random.default_rng(3)
+    n = 1000
+    outs = {"obs": torch.from_numpy(rng.integers(0, 500, size=(2, n, 7))),
+            "reward": torch.from_numpy(rng.normal(size=(2, n))),
+            "truncated": torch.from_numpy(rng.random((2, n)) < 0.1)}
+    bench.dump_outputs(str(tmp_path / "all"), outs, n)
+    assert sorted(os.listdir(tmp_path / "all")) == ["obs.npy", "reward.npy", "truncated.npy"]
+    for k, t in outs.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, t.numpy().astype(np.float64))
+    per_env = 8 * 2 * (7 + 1 + 1)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 100 * (per_env + 8))
+    bench.dump_outputs(str(tmp_path / "a"), outs, n)
+    bench.dump_outputs(str(tmp_path / "b"), outs, n)
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and (np.diff(idx) > 0).all() and idx[-1] < n
+    total = 0
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b)
+        total += a.nbytes
+        if f != "env_index.npy":
+            assert np.array_equal(a, outs[f[:-4]].numpy()[:, idx.astype(np.int64)].astype(np.float64))
+    assert total <= bench.DUMP_BUDGET
+
+
 def test_fold_mode_auto():
     """--fold auto: the in-kernel episode sink for InvMgmt rollouts (and policy
     rollouts), the block fold for single steps and for the other families

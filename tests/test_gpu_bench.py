@@ -42,7 +42,7 @@ def _check_line(d, n_gpus, steps, warmup):
 
 
 def test_bench_single_gpu_line():
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"],
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"],
                        cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -82,6 +82,46 @@ def test_bench_episode_stats_from_timed_batch():
     assert d["episode_stats"]["mean_return"] == d["episode_stats"]["mean_return"]   # not NaN
 
 
+def test_bench_plain_run_is_lean_and_dumps_last_step(gpu, tmp_path):
+    """A plain run times the headline region only (no rollout / graph / configs /
+    CPU baseline: those ride with --full), and --dump-outputs writes the last
+    timed step's outputs: the same env stepped here with the same seeded
+    actions (warm-up calls 0..4, timed calls 0..19 of the 16-batch pool) gives
+    them bit for bit."""
+    import numpy as np
+    import torch
+    import bench
+    import invsim
+    n = 4096
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--n-envs", str(n), "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _last_json(p.stdout)
+    _check_line(d, 1, 20, 5)
+    assert d["dtype"] == "int64" and d["ms_per_step"] == pytest.approx(1e3 * n / d["value"])
+    for k in ("rollout", "graph", "configs", "cpu_baseline"):
+        assert k not in d
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["obs", "reward", "terminated", "truncated"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+
+    env = invsim.InvManagementBacklogEnv(n, device=gpu)
+    g = torch.Generator(device=gpu)
+    g.manual_seed(1234)
+    env.reset(seed=0)
+    acts = bench.make_actions(env, 16, 0, g)
+    for i in list(range(5)) + list(range(20)):
+        o, r, te, tr, _ = env.step(acts[i % 16])
+    assert got["obs"].shape == (1, n, env.obs_dim) and got["reward"].shape == (1, n)
+    assert np.array_equal(got["obs"][0], o.cpu().numpy().astype(np.float64))
+    assert np.array_equal(got["reward"][0], r.cpu().numpy())
+    assert np.array_equal(got["terminated"][0], te.cpu().numpy().astype(np.float64))
+    assert np.array_equal(got["truncated"][0], tr.cpu().numpy().astype(np.float64))
+    assert got["reward"].any() and got["obs"].any()
+
+
 def test_bench_two_ranks_gloo_rehearsal():
     env = dict(os.environ, INVSIM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -100,7 +140,7 @@ def _bench_spawned(extra, rollout=False):
     """plain `bench.py --gpus 2` (no torchrun around it): bench.py starts the ranks"""
     env = dict(os.environ, INVSIM_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--warmup", "5"] + ([] if rollout else ["--no-rollout-line"]) + extra
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--warmup", "5"] + (["--full"] if rollout else ["--no-rollout-line"]) + extra
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     return _last_json(p.stdout)

@@ -92,7 +92,8 @@ def test_bench_under_torchrun_nccl_one_rank():
     env.pop("INVSIM_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           "bench.py", "--gpus", "1", "--steps", "62", "--warmup", "5", "--n-envs", "8192", "--no-cpu-baseline"]
+           "bench.py", "--full", "--gpus", "1", "--steps", "62", "--warmup", "5", "--n-envs", "8192",
+           "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([x for x in p.stdout.strip().splitlines() if x.startswith("{")][-1])

@@ -8,7 +8,7 @@ tail -2 $O/pytest.log
 for w in ${WLS:-invmgmt_backlog invmgmt_lostsales net_backlog}; do
   for ds in numpy philox; do
     for m in step policy; do
-      timeout -k 10 120 python bench.py --workload $w --demand-stream $ds --mode $m --no-cpu-baseline > $O/${w}_${ds}_${m}.json 2> $O/${w}_${ds}_${m}.err || { tail -20 $O/${w}_${ds}_${m}.err; exit 1; }
+      timeout -k 10 120 python bench.py --full --workload $w --demand-stream $ds --mode $m --no-cpu-baseline > $O/${w}_${ds}_${m}.json 2> $O/${w}_${ds}_${m}.err || { tail -20 $O/${w}_${ds}_${m}.err; exit 1; }
     done
   done
 done

@@ -28,7 +28,7 @@ for part in $PARTS; do
     run timeout -k 10 480 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1
     tail -2 $OUT/pytest_gpu.log ;;
   bench)
-    run timeout -k 10 180 python bench.py > $OUT/bench_default.log 2>&1
+    run timeout -k 10 180 python bench.py --full > $OUT/bench_default.log 2>&1
     tail -1 $OUT/bench_default.log | cut -c1-300
     for w in $WLS; do
       run timeout -k 10 120 python bench.py --workload $w $B > $OUT/bench_${w}_step.log 2>&1

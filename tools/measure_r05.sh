@@ -33,7 +33,7 @@ for part in $PARTS; do
     for n in 65536 262144 524288 1048576; do
       P=$OUT/sweep/n$n
       mkdir -p $P
-      run timeout -k 10 180 python bench.py --n-envs $n --steps 400 --warmup 40 $B > $P/bench.json 2>$P/bench.err
+      run timeout -k 10 180 python bench.py --full --n-envs $n --steps 400 --warmup 40 $B > $P/bench.json 2>$P/bench.err
       tail -n1 $P/bench.json | cut -c1-160
       S="--n-envs $n --steps 300 --warmup 30 $B --no-rollout-line"
       R="--n-envs $n --mode rollout --steps 600 --warmup 60 $B"
@@ -55,7 +55,7 @@ for part in $PARTS; do
     for spec in net_backlog:32768 net_backlog:16384 net_backlog:8192 net_backlog:4096 \
                 invmgmt_lostsales:32768 invmgmt_lostsales:8192; do
       w=${spec%%:*}; n=${spec##*:}
-      run timeout -k 10 180 python bench.py --workload $w --n-envs $n --steps 2000 --warmup 100 --no-cpu-baseline \
+      run timeout -k 10 180 python bench.py --full --workload $w --n-envs $n --steps 2000 --warmup 100 --no-cpu-baseline \
           > $OUT/strong/${w}_$n.json 2>$OUT/strong/${w}_$n.err
       tail -n1 $OUT/strong/${w}_$n.json | cut -c1-160
       run timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/strong/trace_${w}_$n -o run -- \
