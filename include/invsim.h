@@ -272,7 +272,12 @@ int invsim_episode_fold_groups(const double *reward, const uint8_t *terminated, 
  * invsim_episode_fold_groups over those rows would (same ret and part bits):
  * the lock-step InvMgmt step and rollout kernels in-kernel, other launches by
  * that fold of their outputs on the same stream (reward / terminated /
- * truncated must then be given).  NULL, NULL detaches.  Not during capture. */
+ * truncated must then be given).  invsim_reset abandons the episodes of the
+ * envs it resets, as the harness's `episode_reward = 0.0` at every reset does
+ * (:368-371): on the reset's stream their ret restarts at +0.0 (every env, or
+ * the masked ones); part is left alone, since nothing finished.  A caller who
+ * folds output rows itself with invsim_episode_fold_groups zeroes ret likewise.
+ * NULL, NULL detaches.  Not during capture. */
 int invsim_set_episode_sink(invsim_handle *h, double *ret, double *part);
 
 /* Debug builds only (make -C csrc ptrs_stats -> invsim/_lib/debug/): PTRS

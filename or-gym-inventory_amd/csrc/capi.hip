@@ -904,6 +904,13 @@ int invsim_reset(invsim_handle *h, const uint8_t *mask, void *obs, void *stream)
         default: return fail(h, INVSIM_EINVAL, "bad handle family");
     }
     if (e != hipSuccess) return hip_fail(h, e, "reset launch");
+    // episode sink: the reset envs abandon their episode, so their running
+    // return restarts (the harness zeroes episode_reward at every reset,
+    // benchmark_InvManagementBacklogEnv.py:368-371); nothing finished, part stays
+    if (h->cm.ep_ret) {
+        e = episode_ret_reset_launch(h->cm.ep_ret, mask, h->N, s);
+        if (e != hipSuccess) return hip_fail(h, e, "episode sink reset");
+    }
     if (mask) {
         h->t_known = false;
     } else {

@@ -44,6 +44,15 @@ __global__ void __launch_bounds__(256) period_fill_kernel(Common cm, int32_t t) 
     if (e < cm.N) cm.period[e] = t;
 }
 
+// A masked reset with an episode sink set: the reset envs abandon their
+// episode, so their running return restarts at +0.0 like the harness's
+// `episode_reward = 0.0` at every reset (benchmark_InvManagementBacklogEnv.py:
+// 368-371); the other envs keep theirs.
+__global__ void __launch_bounds__(256) episode_ret_reset_kernel(double *ret, const uint8_t *mask, int64_t N) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < N) ret[e] = mask[e] ? 0.0 : ret[e];
+}
+
 // Episodic-return reduction of K steps of outputs (the statistics the
 // reference's harness keeps per episode, benchmark_InvManagementBacklogEnv.py:
 // 389-440): per env, ret += reward[k]; at a terminated|truncated step the return
@@ -189,6 +198,13 @@ hipError_t seed_words_launch(const Common &cm, const uint32_t *words, const int3
 hipError_t period_fill_launch(const Common &cm, int32_t t, hipStream_t s) {
     if (cm.N == 0) return hipSuccess;
     hipLaunchKernelGGL(period_fill_kernel, dim3(grid_for(cm.N, 256)), dim3(256), 0, s, cm, t);
+    return hipGetLastError();
+}
+
+hipError_t episode_ret_reset_launch(double *ret, const uint8_t *mask, int64_t N, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    if (!mask) return hipMemsetAsync(ret, 0, (size_t)N * sizeof(double), s);
+    hipLaunchKernelGGL(episode_ret_reset_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, ret, mask, N);
     return hipGetLastError();
 }
 

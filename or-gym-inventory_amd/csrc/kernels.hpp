@@ -604,6 +604,8 @@ hipError_t episode_fold_launch(const double *rew, const uint8_t *term, const uin
 // the EpSink fold of K output rows into per-group partials (no atomics)
 hipError_t episode_fold_groups_launch(const double *rew, const uint8_t *term, const uint8_t *trunc, int32_t K,
                                       int64_t N, double *ret, double *part, hipStream_t s);
+// a reset with an episode sink set: ret[e] = 0 for the reset envs (mask, or all when null)
+hipError_t episode_ret_reset_launch(double *ret, const uint8_t *mask, int64_t N, hipStream_t s);
 
 hipError_t nv_reset_launch(const NvParams &p, const uint8_t *mask, float *obs, hipStream_t s);
 // ahead / slot: the demand lookahead cache state, as for im_run_launch

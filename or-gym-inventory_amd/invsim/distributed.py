@@ -37,6 +37,13 @@ class EpisodeStats:
     tensors (a CPU rehearsal stepping the oracle) are folded with the same
     arithmetic in torch into a single row: there is no device data to hand the
     kernel.
+
+    A reset abandons the running episode of the envs it resets, as the
+    harness's ``episode_reward = 0.0`` at every reset does
+    (``benchmark_InvManagementBacklogEnv.py:368-371``): their running return
+    restarts at 0 and nothing is folded.  An attached env's ``reset`` does
+    this itself (every env, or those of its ``reset_mask``); with
+    ``update_block`` call ``reset_returns`` at each reset of the env.
     """
 
     def __init__(self, num_envs, device):
@@ -58,6 +65,17 @@ class EpisodeStats:
     def reset_acc(self):
         """Forget the folded episodes; running returns carry on."""
         self.part.zero_()
+
+    def reset_returns(self, mask=None):
+        """The env was reset mid-episode (every env, or those of the bool
+        ``mask`` [N]): their running returns restart at 0; nothing is folded."""
+        if mask is None:
+            self.ret.zero_()
+        else:
+            m = torch.as_tensor(mask, device=self.device).to(torch.bool)
+            if m.shape != (self.num_envs,):
+                raise ValueError(f"EpisodeStats.reset_returns: mask must have shape ({self.num_envs},)")
+            self.ret[m] = 0.0
 
     def attach(self, env):
         """Make these statistics `env`'s episode sink: every step / rollout of

@@ -22,6 +22,33 @@ def test_shard_range_partitions():
             assert max(c for _, c in spans) - min(c for _, c in spans) <= 1
 
 
+def test_episode_stats_reset_returns_host():
+    """a reset abandons the running episode: the returns of the reset envs
+    restart at 0, nothing is folded, the others carry on"""
+    from invsim.distributed import EpisodeStats
+    n = 7
+    st = EpisodeStats(n, torch.device("cpu"))
+    r = torch.arange(1, n + 1, dtype=torch.float64)
+    none = torch.zeros(n, dtype=torch.bool)
+    st.update(r, none)
+    st.update(r, none)
+    mask = torch.zeros(n, dtype=torch.bool)
+    mask[::3] = True
+    st.reset_returns(mask)
+    exp = 2 * r
+    exp[::3] = 0.0
+    assert torch.equal(st.ret, exp)
+    assert st.acc.tolist() == [0.0, 0.0, 0.0, float(2 * r.sum())]     # reward sums stay, no episode
+    st.update(r, ~none)                                               # every episode ends
+    assert st.ret.eq(0).all()
+    assert st.allreduce()["episodes"] == n and st.allreduce()["sum"] == float((exp + r).sum())
+    st.update(r, none)
+    st.reset_returns()
+    assert st.ret.eq(0).all() and st.allreduce()["episodes"] == n
+    with pytest.raises(ValueError):
+        st.reset_returns(torch.zeros(n + 1, dtype=torch.bool))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -10,7 +10,10 @@ evaluation harness's running returns (benchmark_InvManagementBacklogEnv.py:
   summed in step order, bit for bit, and the finished-episode statistics its
   episode sums;
 * the other families (no in-kernel fold) take the fallback fold of their
-  outputs, with the same bits as an explicit fold.
+  outputs, with the same bits as an explicit fold;
+* resets: a reset (of every env or a masked one) with the sink attached
+  restarts the reset envs' running returns and folds nothing, against the
+  oracle reset at the same step.
 """
 import numpy as np
 import pytest
@@ -161,6 +164,233 @@ def test_sink_returns_vs_oracle(gpu, oracle):
     assert res["episodes"] == fin.size
     assert res["sum"] == pytest.approx(fin.sum(), rel=1e-12)
     assert res["sum_sq"] == pytest.approx((fin * fin).sum(), rel=1e-12)
+
+
+# ---------------------------------------------------------------- resets with a sink attached
+# invsim_reset abandons the reset envs' episodes: their running return restarts
+# at +0.0 and nothing is folded, as the harness's `episode_reward = 0.0` at every
+# reset (benchmark_InvManagementBacklogEnv.py:368-371).
+N_RST = 3 * 64 + 5          # three full groups and one of 5 envs
+
+
+def _near(got, terms, where):
+    """got against the f64 sum of `terms` in another order: a reordered sum of
+    m terms errs by at most (m - 1) 2**-53 sum|x|; m < 400 here, under 5e-14
+    sum|x|, and 1e-12 leaves about 20x."""
+    terms = np.asarray(terms, np.float64).ravel()
+    exp, tol = terms.sum(), 1e-12 * np.abs(terms).sum()
+    assert abs(float(got) - exp) <= tol, f"{where}: {float(got)!r} != {exp!r} (tol {tol:.3g})"
+
+
+def _group_terms(x, idx, n):
+    """per 64-env group g, the entries of x (one per env of idx) whose env is in g"""
+    idx = np.asarray(idx)
+    return [x[(idx // 64) == g] for g in range((n + 63) // 64)]
+
+
+def _im_oracle_acts(n, K, seed):
+    rng = np.random.default_rng(seed)
+    return rng.integers(-10, 270, size=(K, n, 3)).astype(np.int64)
+
+
+@pytest.mark.parametrize("how", ["plain", "reseed"])
+def test_sink_reset_mid_episode_vs_oracle(gpu, oracle, how):
+    """a reset 12 steps into the episode: the 12 abandoned rewards leave the
+    running returns, the partials keep only their reward sum, and the episode
+    that then finishes is the oracle's 30 steps after its reset"""
+    import invsim
+    from invsim.distributed import EpisodeStats
+    n = N_RST
+    env = invsim.InvManagementBacklogEnv(n, device=gpu)
+    st = EpisodeStats(n, gpu)
+    env.reset(seed=123)
+    st.attach(env)
+    orc = oracle.OracleInvMgmt(n, backlog=True)
+    orc.seed(range(123, 123 + n))
+    orc.reset()
+    acts = _im_oracle_acts(n, 42, 3)
+    dev = torch.from_numpy(acts).to(gpu)
+    env.rollout(dev[:12])
+    for k in range(12):
+        orc.step(acts[k])
+    torch.cuda.synchronize()
+    before = st.part.cpu().numpy().copy()
+    assert np.abs(st.ret.cpu().numpy()).max() > 0          # there is something to abandon
+    if how == "plain":
+        obs, _ = env.reset()
+    else:
+        obs, _ = env.reset(seed=900)
+        orc.seed(range(900, 900 + n))
+    assert np.array_equal(obs.cpu().numpy(), orc.reset())
+    torch.cuda.synchronize()
+    ret = st.ret.cpu().numpy()
+    assert not _bits(st.ret).any(), f"running returns after the reset: max |ret| = {np.abs(ret).max()!r}, not +0.0"
+    part = st.part.cpu().numpy()
+    assert not part[:, :3].any(), "nothing finished: no episode is folded by a reset"
+    assert np.array_equal(part[:, 3].view(np.int64), before[:, 3].view(np.int64)), "reward sums change at a reset"
+    exp = np.zeros(n)
+    rews = []
+    for k in range(12, 17):
+        env.step(dev[k])
+        _, r, _ = orc.step(acts[k])
+        exp = exp + r
+        rews.append(r)
+    torch.cuda.synchronize()
+    got = st.ret.cpu().numpy()
+    assert np.array_equal(got.view(np.int64), exp.view(np.int64)), \
+        f"running returns 5 steps after the reset: max |ret - oracle| = {np.abs(got - exp).max()!r}"
+    env.rollout(dev[17:42])
+    for k in range(17, 42):
+        _, r, tr = orc.step(acts[k])
+        exp = exp + r
+    assert tr.all()
+    torch.cuda.synchronize()
+    assert not _bits(st.ret).any()
+    res = st.allreduce()
+    assert res["episodes"] == n
+    _near(res["sum"], exp, "sum of episode returns")
+    _near(res["sum_sq"], exp * exp, "sum of squared episode returns")
+
+
+def test_sink_masked_reset_vs_oracle(gpu, oracle):
+    """a masked reset 12 steps in: the reset envs' returns restart, the others
+    carry on; the per-env-period launches that follow (im_run_kernel and the
+    fallback fold of its rows) against one oracle per subset"""
+    import invsim
+    from invsim.distributed import EpisodeStats
+    n = N_RST
+    env = invsim.InvManagementBacklogEnv(n, device=gpu)
+    st = EpisodeStats(n, gpu)
+    env.reset(seed=123)
+    st.attach(env)
+    mask = np.zeros(n, bool)
+    mask[::3] = True
+    kept, rst = np.flatnonzero(~mask), np.flatnonzero(mask)
+    orcs = {}
+    for name, idx in (("kept", kept), ("rst", rst)):
+        o = oracle.OracleInvMgmt(len(idx), backlog=True)
+        o.seed([123 + int(i) for i in idx])              # each env's own seed
+        o.reset()
+        orcs[name] = (o, idx)
+    acts = _im_oracle_acts(n, 30, 4)
+    dev = torch.from_numpy(acts).to(gpu)
+    exp = np.zeros(n)
+
+    def orc_steps(k0, k1):
+        for k in range(k0, k1):
+            for o, idx in orcs.values():
+                _, r, tr = o.step(acts[k][idx])
+                exp[idx] = exp[idx] + r
+        return tr
+
+    env.rollout(dev[:12])
+    orc_steps(0, 12)
+    env.reset(options={"reset_mask": torch.from_numpy(mask).to(gpu)})
+    orcs["rst"][0].reset()                               # InvMgmt's reset draws nothing
+    exp[rst] = 0.0
+    for k in range(12, 16):
+        env.step(dev[k])
+    env.rollout(dev[16:22])
+    orc_steps(12, 22)
+    torch.cuda.synchronize()
+    got = st.ret.cpu().numpy()
+    for name, idx in (("kept", kept), ("reset", rst)):
+        assert np.array_equal(got[idx].view(np.int64), exp[idx].view(np.int64)), \
+            f"running returns of the {name} envs: max |ret - oracle| = {np.abs(got[idx] - exp[idx]).max()!r}"
+    assert not st.part.cpu().numpy()[:, :3].any()
+    for k in range(22, 25):
+        env.step(dev[k])
+    env.rollout(dev[25:30])
+    orc_steps(22, 30)                                    # the kept envs truncate at step 29
+    torch.cuda.synchronize()
+    got = st.ret.cpu().numpy()
+    assert not got[kept].view(np.int64).any()
+    assert np.array_equal(got[rst].view(np.int64), exp[rst].view(np.int64))
+    part = st.part.cpu().numpy()
+    for g, x in enumerate(_group_terms(exp[kept], kept, n)):
+        assert part[g, 2] == len(x), g
+        _near(part[g, 0], x, f"group {g} sum of episode returns")
+        _near(part[g, 1], x * x, f"group {g} sum of squared episode returns")
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
+def test_sink_fused_equals_fold_across_reset(gpu, masked):
+    """the sink's reset rule is EpisodeStats.reset_returns on the explicit fold"""
+    import invsim
+    n = N_RST
+    a, b, sa, sb = _twins(invsim.InvManagementBacklogEnv, n, 41, gpu)
+    g = torch.Generator(device=gpu)
+    g.manual_seed(6)
+    mask = None
+    if masked:
+        mask = torch.zeros(n, dtype=torch.bool, device=gpu)
+        mask[::3] = True
+
+    def steps(m, where):
+        for _ in range(m):
+            act = _im_actions(g, 0, n, gpu)
+            a.step(act)
+            _, r, te, tr, _ = b.step(act)
+            sb.update_block(r.reshape(1, -1), te.reshape(1, -1), tr.reshape(1, -1))
+        _check(sa, sb, where)
+
+    steps(9, "9 steps")
+    for x in (a, b):
+        x.reset(options={"reset_mask": mask} if masked else None)
+    sb.reset_returns(mask)
+    _check(sa, sb, "reset")
+    torch.cuda.synchronize()
+    zeroed = sa.ret if mask is None else sa.ret[mask]
+    assert not _bits(zeroed).any()
+    act = _im_actions(g, 30, n, gpu)
+    a.rollout(act)
+    _, r, te, tr = b.rollout(act)
+    sb.update_block(r.contiguous(), te.contiguous(), tr.contiguous())
+    _check(sa, sb, "rollout K=30")
+    steps(3, "3 steps")
+    assert float(sa.acc[2]) == n
+
+
+def test_sink_fallback_family_reset_vs_oracle(gpu, oracle):
+    """a family without the in-kernel fold (Newsvendor): the reset rule is the
+    library's, not a kernel's"""
+    import invsim
+    from invsim.distributed import EpisodeStats
+    n = N_RST
+    env = invsim.NewsvendorEnv(n, device=gpu)
+    st = EpisodeStats(n, gpu)
+    env.reset(seed=9)
+    st.attach(env)
+    orc = oracle.OracleNewsvendor(n)
+    orc.seed(range(9, 9 + n))
+    orc.reset()
+    rng = np.random.default_rng(8)
+    acts = rng.uniform(-50, 2500, size=(47, n, 1)).astype(np.float32)
+    dev = torch.from_numpy(acts).to(gpu)
+    for k in range(7):
+        env.step(dev[k])
+        orc.step(acts[k])
+    torch.cuda.synchronize()
+    assert np.abs(st.ret.cpu().numpy()).max() > 0
+    obs, _ = env.reset()
+    assert np.array_equal(obs.cpu().numpy().view(np.uint32), orc.reset().view(np.uint32))   # its reset draws parameters
+    torch.cuda.synchronize()
+    assert not _bits(st.ret).any(), \
+        f"running returns after the reset: max |ret| = {np.abs(st.ret.cpu().numpy()).max()!r}, not +0.0"
+    env.rollout(dev[7:27])
+    for k in range(27, 47):
+        env.step(dev[k])
+    exp = np.zeros(n)
+    for k in range(7, 47):
+        _, r, tr, _ = orc.step(acts[k])
+        exp = exp + r
+    assert tr.all()
+    torch.cuda.synchronize()
+    assert not _bits(st.ret).any()
+    res = st.allreduce()
+    assert res["episodes"] == n
+    _near(res["sum"], exp, "sum of episode returns")
+    _near(res["sum_sq"], exp * exp, "sum of squared episode returns")
 
 
 def test_sink_refuses_missing_rewards(gpu):
