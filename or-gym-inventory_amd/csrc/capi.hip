@@ -199,7 +199,7 @@ int common_fields(invsim_handle *h, Layout &lay, int64_t &o_rng, int64_t &o_peri
 
 // The A/B launch switches (kernels.hpp Knobs), read from the environment once,
 // here, when a handle is created: the only environment reads of the library.
-// A switch is "0" or "1" exactly; anything else (unset, empty, "false", "on")
+// A flag is "0" or "1" exactly; anything else (unset, empty, "false", "on")
 // keeps the default.
 bool env_flag(const char *name, bool dflt) {
     const char *v = std::getenv(name);
@@ -207,36 +207,65 @@ bool env_flag(const char *name, bool dflt) {
     return v[0] == '1';
 }
 
+// A tri-state starts with '0' or '1' (off / on), else the default (-1).
+int8_t env_tri(const char *name, int8_t dflt) {
+    const char *v = std::getenv(name);
+    return v && (v[0] == '0' || v[0] == '1') ? (int8_t)(v[0] - '0') : dflt;
+}
+
+// A count is a full non-negative decimal, else the default.
+int64_t env_count(const char *name, int64_t dflt) {
+    const char *v = std::getenv(name);
+    if (!v || !v[0]) return dflt;
+    char *end = nullptr;
+    const long long x = std::strtoll(v, &end, 10);
+    return end && !*end && x >= 0 ? (int64_t)x : dflt;
+}
+
+// One row per switch: the kind (flag, tri-state, count) is the member's type.
+struct KnobRow {
+    const char *env;
+    enum { FLAG, TRI, COUNT } kind;
+    union {
+        bool Knobs::*flag;
+        int8_t Knobs::*tri;
+        int64_t Knobs::*count;
+    };
+    constexpr KnobRow(const char *e, bool Knobs::*m) : env(e), kind(FLAG), flag(m) {}
+    constexpr KnobRow(const char *e, int8_t Knobs::*m) : env(e), kind(TRI), tri(m) {}
+    constexpr KnobRow(const char *e, int64_t Knobs::*m) : env(e), kind(COUNT), count(m) {}
+};
+
+// The list of switches.  Defaults are the Knobs member initialisers.
+const KnobRow KNOBS[] = {
+    {"INVSIM_IM_SPLIT", &Knobs::im_split},                // =0: single steps on the one-wave kernel
+    {"INVSIM_IM_ROLL", &Knobs::im_roll},                  // =0: rollouts on the one-wave kernel
+    {"INVSIM_IM_POL_ROLL", &Knobs::im_pol_roll},          // =0: policy rollouts on im_run_kernel
+    {"INVSIM_IM_AHEAD", &Knobs::im_ahead},                // =0: no demand lookahead
+    {"INVSIM_IM_ROLL3O_G2", &Knobs::im_roll3o_g2},        // =1 / =0: two groups per workgroup on / off (default: policy rollouts only)
+    {"INVSIM_IM_ROLL3O_MAX_N", &Knobs::im_roll3o_max_n},  // largest batch for the 3-role rollout
+    {"INVSIM_IM_ROLL_SUB", &Knobs::im_roll_sub},          // 2-role rollouts as back-to-back launches of at most this many envs (0: one launch)
+    {"INVSIM_NV_ROLL", &Knobs::nv_roll},                  // =0: rollouts on nv_run_kernel
+    {"INVSIM_NV_POL_ROLL", &Knobs::nv_pol_roll},          // =0: policy rollouts on nv_run_kernel
+    {"INVSIM_NV_AHEAD", &Knobs::nv_ahead},                // =0: no demand lookahead
+    {"INVSIM_NET_ROLL", &Knobs::net_roll},                // =0: rollouts on net_spec_kernel
+    {"INVSIM_NET_ROLL3", &Knobs::net_roll3},              // =0: net_roll_kernel instead of net_roll3o_kernel
+    {"INVSIM_NET_SPLIT", &Knobs::net_split},              // =0: the step on the one-wave net_step1_kernel
+    {"INVSIM_NET_POL_ROLL", &Knobs::net_pol_roll},        // =0: ConstantOrder rollouts on net_spec_kernel
+    {"INVSIM_NET_AHEAD", &Knobs::net_ahead},              // =0: no demand lookahead
+    {"INVSIM_NET_GENERIC", &Knobs::net_generic},          // =1: the generic kernel for the built-in graphs
+    {"INVSIM_NET_ROLL4_MAX_N", &Knobs::net_roll4_max_n},  // largest batch for the 4-role Net rollout (0: never)
+};
+
 Knobs read_knobs() {
     Knobs k;
-    k.im_split = env_flag("INVSIM_IM_SPLIT", k.im_split);
-    k.im_la_last = env_flag("INVSIM_IM_LA_LAST", k.im_la_last);
-    k.im_roll = env_flag("INVSIM_IM_ROLL", k.im_roll);
-    k.im_pol_roll = env_flag("INVSIM_IM_POL_ROLL", k.im_pol_roll);
-    k.im_ahead = env_flag("INVSIM_IM_AHEAD", k.im_ahead);
-    if (const char *v = std::getenv("INVSIM_IM_ROLL3O_G2"); v && (v[0] == '0' || v[0] == '1'))
-        k.im_roll3o_g2 = (int8_t)(v[0] - '0');
-    auto count = [](const char *name, int64_t &dst) {   // a decimal count, else the default
-        if (const char *v = std::getenv(name); v && v[0]) {
-            char *end = nullptr;
-            const long long x = std::strtoll(v, &end, 10);
-            if (end && !*end && x >= 0) dst = (int64_t)x;
+    for (const KnobRow &r : KNOBS) {
+        switch (r.kind) {
+            case KnobRow::FLAG: k.*r.flag = env_flag(r.env, k.*r.flag); break;
+            case KnobRow::TRI: k.*r.tri = env_tri(r.env, k.*r.tri); break;
+            case KnobRow::COUNT: k.*r.count = env_count(r.env, k.*r.count); break;
         }
-    };
-    count("INVSIM_IM_ROLL3O_MAX_N", k.im_roll3o_max_n);
-    count("INVSIM_IM_ROLL_SUB", k.im_roll_sub);
-    count("INVSIM_NET_ROLLQ_MAX_N", k.net_rollq_max_n);
-    count("INVSIM_NET_ROLL4_MAX_N", k.net_roll4_max_n);
-    k.nv_xcd = env_flag("INVSIM_NV_XCD", k.nv_xcd);
-    k.nv_roll = env_flag("INVSIM_NV_ROLL", k.nv_roll);
-    k.nv_pol_roll = env_flag("INVSIM_NV_POL_ROLL", k.nv_pol_roll);
-    k.nv_ahead = env_flag("INVSIM_NV_AHEAD", k.nv_ahead);
-    k.net_roll = env_flag("INVSIM_NET_ROLL", k.net_roll);
-    k.net_roll3 = env_flag("INVSIM_NET_ROLL3", k.net_roll3);
-    k.net_split = env_flag("INVSIM_NET_SPLIT", k.net_split);
-    k.net_pol_roll = env_flag("INVSIM_NET_POL_ROLL", k.net_pol_roll);
-    k.net_ahead = env_flag("INVSIM_NET_AHEAD", k.net_ahead);
-    k.net_generic = env_flag("INVSIM_NET_GENERIC", k.net_generic);
+    }
     return k;
 }
 

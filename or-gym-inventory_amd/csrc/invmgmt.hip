@@ -647,11 +647,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     };
     // DEC: with the lookahead the dynamics wave loads d itself and the waves
     // meet once (tile complete); otherwise d is handed over at a first barrier
-#ifdef INVSIM_IM_SPLIT_DSYNC   // A/B build only: the round-5 handoff of d through LDS
-    constexpr bool DEC = false;
-#else
     constexpr bool DEC = AHEAD;
-#endif
     const int bid = (int)blockIdx.x;
     TPROBE(0);
     TPROBE_ID();
@@ -1023,9 +1019,9 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
 // Same arithmetic, in the same order, as im_step_regs.
 // The demand wave of the rollout kernels (stream_flat_loop): Poisson demand
 // (:280) of each launch step into the ring dbuf [RD * CH][WAVE], nb barriers
-template <int CH, int RD, class RG, class Stage = NoStage>
+template <int CH, int RD, class RG>
 __device__ __forceinline__ void im_stream_loop(const ImParams &P, RG &g, const double *rhs_l, int64_t *dbuf,
-                                               int lane, int K, int nb, int t_start, Stage stage = Stage()) {
+                                               int lane, int K, int nb, int t_start) {
     StreamPos<RG> pos(P.cm.ph_step);
     stream_flat_loop<CH, RD, 1>(
         K, nb, t_start, P.periods,
@@ -1038,45 +1034,10 @@ __device__ __forceinline__ void im_stream_loop(const ImParams &P, RG &g, const d
             return np_poisson_try(g, P.pc, rhs_l, d);
 #endif
         },
-        [&](int slot, int, int64_t d) { dbuf[slot * WAVE + lane] = d < 0 ? 0 : d; }, stage);
+        [&](int slot, int, int64_t d) { dbuf[slot * WAVE + lane] = d < 0 ? 0 : d; });
 }
 
-// The open-loop rollout's actions of chunk b, staged into the LDS ring
-// act_l [2][CH][2 * M1][WAVE] (32-bit halves) by the demand wave with LDS-DMA
-// loads (global_load_lds_dword: row q of step kk lands at + q * WAVE, lane l at
-// + 4 l): chunk b is read by the dynamics wave between barriers b and b + 1, and
-// its buffer (b & 1) was last read before barrier b - 1.
-template <int CH, int M1>
-struct ImActStage {
-    const int64_t *act;
-    uint32_t *act_l;
-    int64_t N, el;
-    int K, nch;
-    __device__ __forceinline__ void operator()(int b) const {
-        if (b >= nch) return;
-#pragma unroll
-        for (int kk = 0; kk < CH; kk++) {
-            const int k = b * CH + kk;
-            if (k < K) {
-                const uint32_t *src = reinterpret_cast<const uint32_t *>(act + ((int64_t)k * N + el) * M1);
-#pragma unroll
-                for (int q = 0; q < 2 * M1; q++)
-                    __builtin_amdgcn_global_load_lds(
-                        (const void *)(src + q),
-                        (__attribute__((address_space(3))) void *)(act_l + (((b & 1) * CH + kk) * 2 * M1 + q) * WAVE),
-                        4, 0, 0);
-            }
-        }
-    }
-    __device__ __forceinline__ void wait() const { __builtin_amdgcn_s_waitcnt(0); }
-};
 constexpr int IM_AP_LDS = 256;   // alpha**t LDS table of the 3-role rollout (periods <= this)
-// Open-loop actions staged by the demand wave (1) or loaded by the dynamics and
-// obs waves themselves (0, the default: LostSales 32 768 envs, 30-step
-// launches, 63.1-64.1 us against 64.9-65.5 staged, profiles/r04/stage_ab)
-#ifndef IM_ROLL3O_STAGE
-#define IM_ROLL3O_STAGE 0
-#endif
 
 // demand chunk of im_roll3_kernel: 4 launch steps (round 5; 65 536 envs, K = 30:
 // 108.0-109.0 us against 112.1-113.0 with 8, equal at 262 144 envs,
@@ -1452,13 +1413,13 @@ struct ImLt3o : ImLt3<L0, L1, L2> {
     static constexpr int M1 = 3, O = ImLt3<L0, L1, L2>::O;
     // tile, RHS table, demand ring, ibuf [2][CH][M1][WAVE] (inventory, dynamics ->
     // obs wave), abuf [2][CH][M1][WAVE] (requested orders, dynamics -> obs wave;
-    // only with POL or staging), act_l [2][CH][2 M1][WAVE] u32 (actions, demand ->
-    // dynamics wave; only when staging open-loop actions), alpha**t
-    static constexpr size_t abuf_n(bool pol) { return (pol || IM_ROLL3O_STAGE) ? (size_t)2 * CH * M1 * WAVE : 0; }
-    static constexpr size_t actl_n(bool pol) { return (IM_ROLL3O_STAGE && !pol) ? (size_t)2 * CH * 2 * M1 * WAVE : 0; }
+    // only with POL), alpha**t.  Open-loop actions are loaded by the dynamics and
+    // obs waves themselves (staging them through LDS on the demand wave measured
+    // slower: 64.9-65.5 against 63.1-64.1 us, profiles/r04/stage_ab)
+    static constexpr size_t abuf_n(bool pol) { return pol ? (size_t)2 * CH * M1 * WAVE : 0; }
     static constexpr size_t lds(bool pol) {
         return (size_t)WAVE * O * 8 + RHS_LDS_MAX * 8 + (size_t)RD * CH * WAVE * 8 + (size_t)2 * CH * M1 * WAVE * 8 +
-               abuf_n(pol) * 8 + actl_n(pol) * 4 + IM_AP_LDS * 8 + 3 * WAVE * 8;   // + EpLaneLds sums
+               abuf_n(pol) * 8 + IM_AP_LDS * 8 + 3 * WAVE * 8;   // + EpLaneLds sums
     }
 };
 
@@ -1485,9 +1446,8 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     double *rhs_l = reinterpret_cast<double *>(im_tile + WAVE * O);
     int64_t *dbuf = reinterpret_cast<int64_t *>(rhs_l + RHS_LDS_MAX);   // [RD * CH][WAVE]
     int64_t *ibuf = dbuf + G::RD * CH * WAVE;                             // [2][CH][M1][WAVE]
-    int64_t *abuf = ibuf + 2 * CH * M1 * WAVE;                            // [2][CH][M1][WAVE] (POL / staged)
-    uint32_t *act_l = reinterpret_cast<uint32_t *>(abuf + G::abuf_n(POL));  // [2][CH][2 M1][WAVE] (staged)
-    double *ap_l = reinterpret_cast<double *>(act_l + G::actl_n(POL));      // alpha**t, t < periods
+    int64_t *abuf = ibuf + 2 * CH * M1 * WAVE;                            // [2][CH][M1][WAVE] (POL)
+    double *ap_l = reinterpret_cast<double *>(abuf + G::abuf_n(POL));     // alpha**t, t < periods
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t N = P.cm.N;
     const int64_t S = P.cm.Npad;
@@ -1515,12 +1475,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
         for (int q = lane; q < P.periods; q += WAVE) ap_l[q] = P.alpha_pow[q];   // before barrier 0
         ts.flush(lane);
         // barriers 0 .. nch - 1 (demand chunk c ready), nch (the obs wave's last chunk)
-        if (POL || !IM_ROLL3O_STAGE) {
-            im_stream_loop<CH, G::RD>(P, g, rhs_l, dbuf, lane, K, nch + 1, t_start);
-        } else {
-            const ImActStage<CH, M1> stage{io.act, act_l, N, el, K, nch};
-            im_stream_loop<CH, G::RD>(P, g, rhs_l, dbuf, lane, K, nch + 1, t_start, stage);
-        }
+        im_stream_loop<CH, G::RD>(P, g, rhs_l, dbuf, lane, K, nch + 1, t_start);
         if (valid) P.cm.rng.store_state(e, g);
         TWAIT();
         TPROBE_W(6);
@@ -1541,7 +1496,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                 if (v == IM_WIDE) wv[a][i] = P.alog[base + i];
             }
         }
-        constexpr bool HANDED = POL || IM_ROLL3O_STAGE;   // requested orders from the dynamics wave
+        constexpr bool HANDED = POL;   // requested orders from the dynamics wave
         int64_t nact[M1];
 #pragma unroll
         for (int i = 0; i < M1; i++) nact[i] = HANDED ? 0 : io.act[el * M1 + i];
@@ -1644,10 +1599,9 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     double met[MD];
 #pragma unroll
     for (int q = 0; q < MD; q++) met[q] = (POL && pol.metrics) ? pol.metrics[el * MD + q] : 0.0;
-    constexpr bool STAGED = !POL && IM_ROLL3O_STAGE;
     int64_t nact[M1];
 #pragma unroll
-    for (int i = 0; i < M1; i++) nact[i] = (POL || STAGED) ? 0 : io.act[el * M1 + i];
+    for (int i = 0; i < M1; i++) nact[i] = POL ? 0 : io.act[el * M1 + i];
     int64_t dlast = 0;
     bool last_real = false;
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
@@ -1657,22 +1611,18 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     EpLaneLds ep;
     bool ep_done = false;
     if (ep_part) ep.init(reinterpret_cast<double *>(ap_l + IM_AP_LDS), lane, valid ? P.cm.ep_ret[e] : 0.0);
-    wg_lds_sync();   // barrier 0: demand chunk 0 (and its actions when staged, alpha**t) ready
+    wg_lds_sync();   // barrier 0: demand chunk 0 (and alpha**t) ready
     for (int c = 0; c < nch; c++) {
         const int64_t *db = dbuf + (c % G::RD) * CH * WAVE;
         int64_t *ib = ibuf + (c & 1) * CH * M1 * WAVE;
         int64_t *ab = abuf + (c & 1) * CH * M1 * WAVE;
-        const uint32_t *al = act_l + (c & 1) * CH * 2 * M1 * WAVE;
         for (int kk = 0; kk < CH && c * CH + kk < K; kk++) {
             const int k = c * CH + kk;
             const int64_t oi = (int64_t)k * N + e;
             int64_t req[M1];
 #pragma unroll
-            for (int i = 0; i < M1; i++)
-                req[i] = !STAGED ? nact[i]
-                                 : (int64_t)((uint64_t)al[(kk * 2 * M1 + 2 * i) * WAVE + lane] |
-                                             ((uint64_t)al[(kk * 2 * M1 + 2 * i + 1) * WAVE + lane] << 32));
-            if (!POL && !STAGED && k + 1 < K) {    // prefetch the next step's actions
+            for (int i = 0; i < M1; i++) req[i] = nact[i];
+            if (!POL && k + 1 < K) {    // prefetch the next step's actions
 #pragma unroll
                 for (int i = 0; i < M1; i++) nact[i] = io.act[((int64_t)(k + 1) * N + el) * M1 + i];
             }
@@ -1774,7 +1724,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                         hv[i][0] = req[i];
                     }
                 }
-                if (POL || STAGED) {
+                if (POL) {
 #pragma unroll
                     for (int i = 0; i < M1; i++) ab[(kk * M1 + i) * WAVE + lane] = req[i];   // the order -> obs wave
                 }
@@ -1960,7 +1910,9 @@ hipError_t im_run_launch_ph(const ImParams &p, int M1, bool backlog, int t_u, co
         const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;
         const dim3 grid2(grid.x + gla), block2(2 * WAVE);
         const int cur = slot;
-        const int la0 = p.cm.kn.im_la_last ? (int)grid.x : 0;
+        // the lookahead workgroups are the first gla of the grid; la0 stays a kernel
+        // argument because folding it into the kernel changed its register allocation
+        const int la0 = 0;
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
@@ -2037,7 +1989,9 @@ hipError_t im_run_launch(const ImParams &p, int M1, bool backlog, int t_u, const
         const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;   // lookahead workgroups
         const dim3 grid2(grid.x + gla);
         const int cur = slot;
-        const int la0 = p.cm.kn.im_la_last ? (int)grid.x : 0;   // lookahead workgroups first (default) or last
+        // the lookahead workgroups are the first gla of the grid; la0 stays a kernel
+        // argument because folding it into the kernel changed its register allocation
+        const int la0 = 0;
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \

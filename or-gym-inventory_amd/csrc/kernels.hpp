@@ -96,31 +96,34 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // variables).  capi.hip reads the environment ONCE, when a handle is created
 // (read_knobs), into Common::kn; the launchers read only these fields, so a
 // variable set after creation changes nothing.  Kernels ignore them.
+// capi.hip's KNOBS table names each field's variable and what it switches;
+// the initialisers here are the defaults.
 struct Knobs {
-    bool im_split = true;            // INVSIM_IM_SPLIT=0: single steps on the one-wave kernel
-    bool im_la_last = false;         // INVSIM_IM_LA_LAST=1: lookahead workgroups at the end of the grid
-    bool im_roll = true;             // INVSIM_IM_ROLL=0: rollouts on the one-wave kernel
-    bool im_pol_roll = true;         // INVSIM_IM_POL_ROLL=0: policy rollouts on im_run_kernel
-    bool im_ahead = true;            // INVSIM_IM_AHEAD=0: no demand lookahead
-    int8_t im_roll3o_g2 = -1;        // INVSIM_IM_ROLL3O_G2=1 / =0: two groups per workgroup on / off
-                                     //   (-1: policy rollouts only)
-    bool nv_xcd = true;              // INVSIM_NV_XCD=0: lookahead workgroups adjacent, not XCD-paired
-    bool nv_roll = true;             // INVSIM_NV_ROLL=0: rollouts on nv_run_kernel
-    bool nv_pol_roll = true;         // INVSIM_NV_POL_ROLL=0: policy rollouts on nv_run_kernel
-    bool nv_ahead = true;            // INVSIM_NV_AHEAD=0: no demand lookahead
-    bool net_roll = true;            // INVSIM_NET_ROLL=0: rollouts on net_spec_kernel
-    bool net_roll3 = true;           // INVSIM_NET_ROLL3=0: net_roll_kernel instead of net_roll3o_kernel
-    bool net_split = true;           // INVSIM_NET_SPLIT=0: the step on the one-wave net_step1_kernel
-    bool net_pol_roll = true;        // INVSIM_NET_POL_ROLL=0: ConstantOrder rollouts on net_spec_kernel
-    bool net_ahead = true;           // INVSIM_NET_AHEAD=0: no demand lookahead
-    bool net_generic = false;        // INVSIM_NET_GENERIC=1: the generic kernel for the built-in graphs
-    int64_t im_roll3o_max_n = 32768; // INVSIM_IM_ROLL3O_MAX_N: largest batch for the 3-role rollout
-    int64_t im_roll_sub = 65536;     // INVSIM_IM_ROLL_SUB: 2-role rollouts as back-to-back launches of at most this many envs (0: one launch)
-    int64_t net_roll4_max_n = 16384; // INVSIM_NET_ROLL4_MAX_N: largest batch for the 4-role Net rollout (0: never)
-    int64_t net_rollq_max_n = 0;     // INVSIM_NET_ROLLQ_MAX_N: largest batch for the 16-lane-row Net rollout
-                                     //   (net_rollq_kernel; 0 = never, the default: measured 6 % slower than
-                                     //   net_roll3o_kernel at 4 096 envs and 1.9x slower at 8 192)
+    bool im_split = true;
+    bool im_roll = true;
+    bool im_pol_roll = true;
+    bool im_ahead = true;
+    int8_t im_roll3o_g2 = -1;        // tri-state: -1 = policy rollouts only
+    bool nv_roll = true;
+    bool nv_pol_roll = true;
+    bool nv_ahead = true;
+    bool net_roll = true;
+    bool net_roll3 = true;
+    bool net_split = true;
+    bool net_pol_roll = true;
+    bool net_ahead = true;
+    bool net_generic = false;
+    int64_t im_roll3o_max_n = 32768;
+    int64_t im_roll_sub = 65536;
+    int64_t net_roll4_max_n = 16384;
+    // Common is a by-value argument of every kernel, so the size of Knobs sets the
+    // offsets of the fields behind it and with them how the kernels' scalar
+    // argument loads align.  8 B shorter, the LostSales 32 768-env step measured
+    // 6.08 against 5.98 us with otherwise identical instructions: keep 48 B, or
+    // measure the step kernels again.
+    char pad_[8] = {};
 };
+static_assert(sizeof(Knobs) == 48, "changes every kernel's argument offsets: see pad_");
 
 struct Common {
     int64_t N;       // envs in this handle
@@ -458,18 +461,14 @@ struct TableStage {
 // reads them in a later kernel or on the host, and streaming them past L2 leaves
 // less dirty data for the end-of-kernel write-back (measured on MI355X: +7 %
 // step, +15 % rollout throughput for InvMgmt).  State stores (st_store) stay
-// cached unless INVSIM_NT_STATE (profiling experiment).
+// cached.
 template <typename V>
 __device__ __forceinline__ void out_store(V *p, V v) {
     __builtin_nontemporal_store(v, p);
 }
 template <typename V>
 __device__ __forceinline__ void st_store(V *p, V v) {
-#ifdef INVSIM_NT_STATE
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
 // Copy `count` elements of an LDS tile to global memory, 16 B per lane.
@@ -548,30 +547,14 @@ __device__ __forceinline__ bool np_poisson_try(G &g, const PtrsConst &c, const d
 // the consumer is done with the slot's previous step j - RD*CH (barrier
 // (j / CH - RD) + 1 passed).  A NEXT_STEP reset step (t >= T) draws nothing.
 //   draw(j, r, k) -> bool: one attempt for draw r of launch step j; put(slot, r, k): store it
-// A stream wave can also stage other per-step inputs of chunk b for the
-// consumer waves (stage(b), e.g. LDS-DMA loads of the actions): issued when the
-// wave starts chunk b (right after barrier b - 1), waited for (stage.wait())
-// before barrier b.  The stream wave issues no global stores, so that wait
-// waits for nothing else; the consumers then load nothing from global memory in
-// their loops, where a load would wait for their own earlier stores (vmcnt
-// counts stores, and completes in order).
-struct NoStage {
-    __device__ __forceinline__ void operator()(int) const {}
-    __device__ __forceinline__ void wait() const {}
-};
-
-template <int CH, int RD, int RL, class Draw, class Put, class Stage = NoStage>
-__device__ __forceinline__ void stream_flat_loop(int K, int nb, int t, int T, Draw draw, Put put,
-                                                 Stage stage = Stage()) {
+template <int CH, int RD, int RL, class Draw, class Put>
+__device__ __forceinline__ void stream_flat_loop(int K, int nb, int t, int T, Draw draw, Put put) {
     static_assert(RD >= 2, "the ring needs two chunks");
     int j = 0, r = 0, b = 0;
-    stage(0);
     for (;;) {
         while (b < nb && __all(j >= min((b + 1) * CH, K))) {
-            stage.wait();
             roll_wg_sync();                        // barrier b: chunk b drawn
             b++;
-            stage(b);
         }
         if (b == nb) break;
         if (j < K && j / CH - RD + 2 <= b) {

@@ -559,7 +559,7 @@ __device__ __forceinline__ int64_t nv_poisson_c(G &g, const PtrsConst &c, const 
 // !PRODUCE the host launches no lookahead workgroups (there is nothing to commit).
 template <int LT, bool HIT, bool PRODUCE, class RG = Pcg>
 __global__ void __launch_bounds__(WAVE)
-nv_step1_kernel(NvParams P, int sc, StepIO<float, float> io, int cur, int gla, int xcdpair) {
+nv_step1_kernel(NvParams P, int sc, StepIO<float, float> io, int cur, int gla) {
     extern __shared__ __attribute__((aligned(16))) float nv_tile[];
     const int lane = threadIdx.x;
     const int64_t N = P.cm.N;
@@ -576,13 +576,14 @@ nv_step1_kernel(NvParams P, int sc, StepIO<float, float> io, int cur, int gla, i
         // (bid even: PTRS for lam >= 10 and lam == 0; odd: the multiplication
         // method for 0 < lam < 10), so a wave runs one branch, not both one
         // after the other; a lane works only on the workgroup of its env's branch
-        // PRODUCE: which 64 envs and which branch.  xcdpair: the two workgroups of
-        // a group are 8 apart (blocks of 16 = 8 groups x 2 branches), so both --
-        // and the group's step workgroup, when gla % 8 == 0 -- run on the same XCD
+        // PRODUCE: which 64 envs and which branch.  The two workgroups of a group
+        // are 8 apart (blocks of 16 = 8 groups x 2 branches), so both -- and the
+        // group's step workgroup, when gla % 8 == 0 -- run on the same XCD
         // (dispatch is round-robin over the 8) and share its L2 for the rows both
-        // read (state, increment, mu); else adjacent (bid >> 1, bid & 1)
+        // read (state, increment, mu); the last partial block is adjacent
+        // (bid >> 1, bid & 1)
         int grp = PRODUCE ? bid >> 1 : bid, brn = bid & 1;
-        if (PRODUCE && xcdpair && (bid | 15) < gla) {
+        if (PRODUCE && (bid | 15) < gla) {
             grp = ((bid >> 4) << 3) + (bid & 7);
             brn = (bid >> 3) & 1;
         }
@@ -1605,12 +1606,11 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
             const int gla = hit ? (produce ? 2 : (ph ? 0 : 1)) * (int)grid_for(p.cm.N, WAVE) : 0;
             const dim3 grid2(grid.x + gla);
             const int cur = slot;
-            const int xp = p.cm.kn.nv_xcd ? 1 : 0;
 #define S_(X)                                                                                                \
     do {                                                                                                     \
-        if (hit && produce) hipLaunchKernelGGL((nv_step1_kernel<X, true, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla, xp);  \
-        else if (hit) hipLaunchKernelGGL((nv_step1_kernel<X, true, false, RG>), grid2, block, lds, s, p, t_u, io, cur, gla, xp);       \
-        else hipLaunchKernelGGL((nv_step1_kernel<X, false, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla, xp);                \
+        if (hit && produce) hipLaunchKernelGGL((nv_step1_kernel<X, true, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);      \
+        else if (hit) hipLaunchKernelGGL((nv_step1_kernel<X, true, false, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);           \
+        else hipLaunchKernelGGL((nv_step1_kernel<X, false, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);                    \
     } while (0)
             NV_LT_SWITCH(S_)
 #undef S_

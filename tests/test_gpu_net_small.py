@@ -1,11 +1,8 @@
 """NetInvMgmt rollouts for small per-GPU shards (SURVEY row h*, VERDICT r05
 item 3): net_roll4_kernel puts the period profit on a wave of its own (the
-default up to 16 384 envs), and net_rollq_kernel (opt-in) spreads one env's
-edge work over a 16-lane row (clamp-scan over each supplier's links, row
-gathers for the per-node sums, a node-order scan for the period profit;
-netspec.hip).  Bar: bit-identical to the one-env-per-lane 3-role
-net_roll3o_kernel (INVSIM_NET_ROLL4_MAX_N=0 / INVSIM_NET_ROLLQ_MAX_N=0) and
-to the C oracle stepping the same seeds (network_management.py:436-635)."""
+default up to 16 384 envs; netspec.hip).  Bar: bit-identical to the 3-role
+net_roll3o_kernel (INVSIM_NET_ROLL4_MAX_N=0) and to the C oracle stepping
+the same seeds (network_management.py:436-635)."""
 import numpy as np
 import pytest
 import torch
@@ -41,19 +38,14 @@ def _pair(gpu, monkeypatch, kernel, graph, backlog, n, periods, mode, stream):
     mk = (lambda: invsim.NetInvMgmtMasterEnv(n, device=gpu, graph=mk_g(), backlog=backlog, num_periods=periods,
                                              autoreset_mode=mode, demand_stream=stream))
     monkeypatch.setenv("INVSIM_NET_ROLL4_MAX_N", "0")
-    monkeypatch.setenv("INVSIM_NET_ROLLQ_MAX_N", "0")
     ref = mk()
-    if kernel == "rollq":
-        monkeypatch.setenv("INVSIM_NET_ROLLQ_MAX_N", "100000")
-    else:
-        monkeypatch.setenv("INVSIM_NET_ROLL4_MAX_N", "100000")
+    monkeypatch.setenv("INVSIM_NET_ROLL4_MAX_N", "100000")
     env = mk()
     monkeypatch.delenv("INVSIM_NET_ROLL4_MAX_N")
-    monkeypatch.delenv("INVSIM_NET_ROLLQ_MAX_N")
     return [env, ref]
 
 
-@pytest.mark.parametrize("kernel", ["roll4", "rollq"])
+@pytest.mark.parametrize("kernel", ["roll4"])
 @pytest.mark.parametrize("graph,backlog,n,periods,mode,stream", CASES)
 def test_small_shard_rollout_equals_roll3o(gpu, monkeypatch, kernel, graph, backlog, n, periods, mode, stream):
     envs = _pair(gpu, monkeypatch, kernel, graph, backlog, n, periods, mode, stream)
@@ -79,7 +71,7 @@ def test_small_shard_rollout_equals_roll3o(gpu, monkeypatch, kernel, graph, back
             assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("kernel", ["roll4", "rollq"])
+@pytest.mark.parametrize("kernel", ["roll4"])
 @pytest.mark.parametrize("graph", ["default", "custom"])
 def test_small_shard_rollout_vs_oracle(gpu, oracle, monkeypatch, kernel, graph):
     """4 096 envs (one rank's shard of config 5 over 8 GPUs): a 61-step fused
@@ -88,10 +80,7 @@ def test_small_shard_rollout_vs_oracle(gpu, oracle, monkeypatch, kernel, graph):
     from invsim.topology import custom_graph, default_graph
     n, T, K = 4096, 30, 61
     g = default_graph() if graph == "default" else custom_graph()
-    if kernel == "rollq":
-        monkeypatch.setenv("INVSIM_NET_ROLLQ_MAX_N", "100000")   # net_rollq_kernel (opt-in)
     env = invsim.NetInvMgmtBacklogEnv(n, device=gpu, graph=g)   # net_roll4_kernel by default at this size
-    monkeypatch.delenv("INVSIM_NET_ROLLQ_MAX_N", raising=False)
     orc = oracle.OracleNet(n, graph=g)
     orc.seed(range(500, 500 + n))
     e_obs = orc.reset()

@@ -1,4 +1,5 @@
-"""Tables of tools/measure_r05.sh outputs (profiling aid).
+"""Tables of the outputs of tools/measure_r05.sh (a per-visit script, now only
+in git history; profiling aid).
 
   python tools/sweep_summary.py gpurun_out/meas_r05 profiles/r05
 
