@@ -57,6 +57,7 @@ struct invsim_handle {
     Common cm{};
     NvParams nv{};
     ImParams im{};
+    std::vector<double> im_ap;  // host copy of im.alpha_pow (the split step takes alpha ** t by value)
     NetParams net{};
     int32_t im_m1 = 0;
     bool im_backlog = false;
@@ -335,7 +336,6 @@ int finish_create(invsim_handle *h, invsim_handle **out, int rc) {
     return INVSIM_OK;
 }
 
-int64_t pad_n(int64_t n) { return std::max<int64_t>(256, (n + 255) / 256 * 256); }
 
 // Host table of PTRS's right-hand side  -lam + k*log(lam) - loggam(k+1)  for the
 // k that occur in practice (lam +- 12 sd), evaluated with the host libm exactly as
@@ -557,6 +557,7 @@ int invsim_create_invmgmt(const invsim_invmgmt_spec *s, int64_t n, int32_t devic
         }
         p.pc = pc;
         p.alpha_pow = tab<double>(h, o_ap);
+        h->im_ap = ap;
         p.user_D = tab<int64_t>(h, o_ud);
         p.I = at<int64_t>(h, o_I);
         p.B = at<int64_t>(h, o_B);
@@ -993,7 +994,7 @@ static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, do
         case INVSIM_INVMGMT: {
             StepIO<int64_t, int64_t> io{K, (const int64_t *)actions, (int64_t *)obs, reward, terminated, truncated,
                                         (int64_t *)final_obs};
-            e = im_run_launch(h->im, h->im_m1, h->im_backlog, t_u, pol, io, h->la_valid, h->la_slot, sunk, s);
+            e = im_run_launch(h->im, h->im_ap.data(), h->im_m1, h->im_backlog, t_u, pol, io, h->la_valid, h->la_slot, sunk, s);
             break;
         }
         case INVSIM_NETINVMGMT: {

@@ -31,6 +31,19 @@ namespace {
 
 #ifdef INVSIM_TIMING
 __device__ uint64_t g_tbuf[TB_WAVES * TB_PROBES];
+// im_split_kernel: the time at which a wave holds its first kernel-argument
+// values, g_targ[workgroup][0 window wave / lookahead workgroup, 1 dynamics
+// wave].  `dep` is an argument-derived scalar: the empty asm needs it in an
+// SGPR, so the timestamp follows the wait on the argument loads (if any)
+__device__ uint64_t g_targ[TB_WAVES * 2];
+#define TPROBE_ARGS(col, tid, dep)                                                             \
+    do {                                                                                       \
+        asm volatile("" ::"s"(dep));                                                           \
+        if (threadIdx.x == (tid) && blockIdx.x < TB_WAVES)                                     \
+            g_targ[blockIdx.x * 2 + (col)] = __builtin_amdgcn_s_memrealtime();                 \
+    } while (0)
+#else
+#define TPROBE_ARGS(col, tid, dep) do {} while (0)
 #endif
 
 // obs-window entries per lane kept in registers: the (lt_max - 1) * M1 entries
@@ -616,16 +629,64 @@ __device__ __forceinline__ void wg_lds_sync() {
 // RG = PhiloxGen (the fast stream, invmgmt_ph.hip): the same lookahead, but a
 // draw is a function of (key, launch step) only, so the cache holds just the
 // next step's demand (row 2 of a slot) and no generator state is read or written.
+//
+// Arguments.  The first eight (14 dwords: IM_HOT_DWORDS, the Makefile's
+// -amdgpu-kernarg-preload-count) are what a wave needs to pick its role and to
+// form the addresses of its up-front loads; as leading scalar parameters they
+// are in SGPRs when the wave starts (kernarg preload), so its first vector
+// loads wait for no scalar load.  A struct parameter is never preloaded, hence
+// no struct here.  In front of those loads the kernel reads no P field, no
+// value behind a pointer and no blockDim / gridDim (the hidden argument block).
+//   act, Ip, Bp, Rr, a32   io.act, P.I, P.B, P.Rring, P.alog32
+//   Acur                   the current lookahead slot (P.ahead + cur * 4 * Npad), or null
+//   n32                    N (the row stride follows: pad_n); the lookahead
+//                          workgroups are the first ceil(N / 128) of an AHEAD grid
+//   hw                     ImHot: the window's first ring slot, last logged row and
+//                          depth, and the three arrival ring rows, packed by the
+//                          host (im_split_args); 0 = not packable, derive from P
+// Behind P, by value, what the host knows at launch: alpha ** t (apow), the
+// window's rows and logged entries (n, nw), the truncation flag (t + 1 >= periods).
+//
+// im_split_waves: the waves per SIMD the register allocator must keep (1 = no
+// request, as without the attribute).  With the leading arguments held in
+// SGPRs one shape fell an occupancy step below what it had with all arguments
+// loaded late (2 stages, dist 2-4, lookahead hit, PCG64: 97 VGPRs for 96);
+// asking for that step keeps it, with no scratch (91 VGPRs).  The same request
+// for the 6-stage backlog inline-draw variants or the Philox 2-stage ones
+// only moved registers into scratch, so they carry none.
+constexpr int im_split_waves(int m1, bool npd, bool ahead, bool counter) {
+    return (m1 == 2 && npd && ahead && !counter) ? 5 : 1;
+}
 template <int M1, bool BACKLOG, bool NPD, bool AHEAD, class RG = Pcg>
 __global__ void __launch_bounds__(2 * WAVE)
-im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0, int gla) {
+    __attribute__((amdgpu_waves_per_eu(im_split_waves(M1, NPD, AHEAD, RG::kCounter))))
+im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr, const uint32_t *a32, uint64_t *Acur,
+                int32_t n32, uint32_t hw, ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, double apow,
+                int n, int nw, int trunc) {
     extern __shared__ __attribute__((aligned(16))) int64_t im_tile[];
-    const int64_t N = P.cm.N;
-    const int64_t S = P.cm.Npad;
-    double *rhs_l = reinterpret_cast<double *>(im_tile + (int64_t)WAVE * M1 * (P.lt_max + 1));
-    uint64_t *Acur = P.ahead ? P.ahead + (int64_t)cur * 4 * S : nullptr;
-    uint64_t *Anxt = P.ahead ? P.ahead + (int64_t)(cur ^ 1) * 4 * S : nullptr;
-    const int64_t udem = P.user_D[t];
+    const int64_t N = n32;
+    const int64_t S = pad_n(N);
+    const int la0 = 0;                                   // the lookahead workgroups lead the grid
+    const int gla = AHEAD ? (int)((n32 + 2 * WAVE - 1) / (2 * WAVE)) : 0;
+    // what the load addresses need, from the packed word (ImHot, M1 = 3) or,
+    // where the host could not pack it, derived as the host does (im_split_args):
+    //   D      window depth (P.lt_max)
+    //   slot0  ring slot of the window's first row, (t + 1 - n) mod D
+    //   rmax   last window row that holds a logged order
+    //   arrival_row(i)  R-ring row of stage i's arrival, ring_off[i] + t mod L[i],
+    //                   or -1: nothing arrives (L[i] = 0, or t < L[i])
+    const bool hot = M1 == ImHot::M1 && __builtin_expect(ImHot::packed(hw), 1);
+    const int D = hot ? ImHot::depth(hw) : P.lt_max;
+    const int slot0 = hot ? ImHot::slot0(hw) : D > 0 ? (int)((uint32_t)(t + 1 - n) % (uint32_t)D) : 0;
+    const int rmax = hot ? ImHot::rmax(hw) : nw > 0 ? nw / M1 - 1 : 0;
+    auto arrival_row = [&](int i) -> int {
+        if (hot) return ImHot::row(hw, i) == ImHot::NOARR ? -1 : ImHot::row(hw, i);
+        const int L = P.L[i];
+        return (L > 0 && t >= L) ? P.ring_off[i] + (int)((uint32_t)t % (uint32_t)L) : -1;
+    };
+    double *rhs_l = reinterpret_cast<double *>(im_tile + (int64_t)WAVE * M1 * (D + 1));
+    // the other lookahead slot (a P field and an argument behind P: formed where it is stored to)
+    auto anxt = [&]() -> uint64_t * { return P.ahead ? P.ahead + (int64_t)(cur ^ 1) * 4 * S : nullptr; };
     auto stage_table = [&](int lane) {
         TableStage ts;
         ts.dst = rhs_l;
@@ -641,7 +702,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
         int64_t x = 20 + (int64_t)(g.lo & 3);
         g.next64();
 #else
-        int64_t x = NPD ? np_demand(g, u32, P.nd) : (P.dist == 5) ? udem : env_poisson(g, P.pc, rhs_l);
+        int64_t x = NPD ? np_demand(g, u32, P.nd) : (P.dist == 5) ? P.user_D[t] : env_poisson(g, P.pc, rhs_l);
 #endif
         return x < 0 ? 0 : x;
     };
@@ -652,11 +713,13 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     TPROBE(0);
     TPROBE_ID();
     if (AHEAD && bid >= la0 && bid < la0 + gla) {   // ---- lookahead workgroup: 128 envs, one per lane
+        TPROBE_ARGS(0, 0, (int)N + gla);
         const int64_t e = (int64_t)(bid - la0) * (2 * WAVE) + threadIdx.x;
         const bool valid = e < N;
         const int64_t ee = valid ? e : N - 1;
-        TableStage ts = stage_table((int)(threadIdx.x & (WAVE - 1)));
+        TableStage ts;
         if constexpr (RG::kCounter) {   // the fast stream: the draw of launch step ph_step + 1
+            ts = stage_table((int)(threadIdx.x & (WAVE - 1)));
             RG g;
             P.cm.rng.load(ee, g);
             g.set_step(P.cm.ph_step + 1);
@@ -664,15 +727,19 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
             uint64_t u32 = 0;
             ts.flush((int)(threadIdx.x & (WAVE - 1)));
             const int64_t dn = draw(g, u32);
-            if (valid) st_store(Anxt + 2 * S + e, (uint64_t)dn);
+            if (valid) st_store(anxt() + 2 * S + e, (uint64_t)dn);
             return;
         }
+        // the slot's rows first: their addresses come from the leading arguments
+        // alone; the increments' pointers and the table's are P fields (they
+        // do not fit into the 14 dwords)
         Pcg g;
         g.hi = Acur[ee];
         g.lo = Acur[S + ee];
+        uint64_t u32 = NPD ? Acur[3 * S + ee] : 0;
+        ts = stage_table((int)(threadIdx.x & (WAVE - 1)));
         g.inc_hi = P.cm.rng.inc_hi[ee];
         g.inc_lo = P.cm.rng.inc_lo[ee];
-        uint64_t u32 = NPD ? Acur[3 * S + ee] : 0;
         PtrsJumpLane jt;
         jt.load((int)(threadIdx.x & (WAVE - 1)));
         ts.flush((int)(threadIdx.x & (WAVE - 1)));   // each wave writes the whole (identical) table
@@ -689,6 +756,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
             dn = draw(g, u32);
         TPROBE(2);
         if (valid) {
+            uint64_t *const Anxt = anxt();
             st_store(Anxt + e, g.hi);
             st_store(Anxt + S + e, g.lo);
             st_store(Anxt + 2 * S + e, (uint64_t)dn);
@@ -704,21 +772,16 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     const int64_t e = e0 + lane;
     const bool valid = e < N;
     const int nvalid = (int)((N - e0) < WAVE ? (N - e0) : WAVE);
-    const int D = P.lt_max;
     const int O = M1 * (D + 1);
     int64_t *trow = im_tile + (int64_t)lane * O;
     int64_t *w = trow + M1;
     int64_t *dsh = reinterpret_cast<int64_t *>(rhs_l + RHS_LDS_MAX);
-    const int t1 = t + 1;
-    const int n = D > 0 ? (t1 < D ? t1 : D) : 0;                    // window rows incl. the newest
-    const int nw = n > 0 ? (n - 1) * M1 : 0;
     // the tile halves each wave stores (16-byte aligned: an even int64 count)
     const int64_t tcount = (int64_t)nvalid * O;
     const int64_t thalf = ((tcount / 2) + 1) & ~(int64_t)1;
     constexpr int WL = im_wlane(M1);
     const bool wreg = (D - 1) * M1 <= WL;   // launch-uniform
     // window rows t+1-n .. t-1 (:380), loaded whole (see im_step_regs)
-    const int slot0 = D > 0 ? (int)((uint32_t)(t1 - n) % (uint32_t)D) : 0;
     auto wrow = [&](int r) -> int64_t {
         int slot = slot0 + r;
         slot = slot >= D ? slot - D : slot;
@@ -738,8 +801,8 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     constexpr int WD = (RWN - RW) * M1 > 0 ? (RWN - RW) * M1 : 1;
     const bool wsplit = DEC && wreg && RW < RWN;
     const int u_dyn = wsplit ? RW * M1 : WL;   // log entries u_dyn <= u < nw: the dynamics wave's
-    const int rmax = nw > 0 ? nw / M1 - 1 : 0;
     if (demand_wave) {
+        TPROBE_ARGS(0, 0, (int)N + gla);
         const int64_t ee = valid ? e : N - 1;        // padded lanes: the last env's stream
         TableStage ts;
         RG g;
@@ -763,7 +826,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
                 for (int i = 0; i < M1; i++) wv[r * M1 + i] = (uint32_t)(r + i);
 #else
                 if (r < RW || !wsplit) {
-                    const uint32_t *src = P.alog32 + wrow(r < rmax ? r : rmax);
+                    const uint32_t *src = a32 + wrow(r < rmax ? r : rmax);
 #pragma unroll
                     for (int i = 0; i < M1; i++) wv[r * M1 + i] = src[i];
                 } else {
@@ -820,6 +883,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
         wg_lds_sync();   // tile complete
         store_tile<(M1 * 11 * WAVE * 8 / 2 + 16 * WAVE - 1) / (16 * WAVE)>(im_tile, io.obs + e0 * O,
                                                                           thalf < tcount ? thalf : tcount, lane);
+        uint64_t *const Anxt = AHEAD ? nullptr : anxt();
         if (!AHEAD && Anxt) {    // lookahead after an inline draw (first step after invalidation)
             if constexpr (RG::kCounter) {
                 g.set_step(P.cm.ph_step + 1);
@@ -842,17 +906,8 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     }
     // ---- dynamics wave
     TPROBE_AT(3, WAVE);
-    const double apow = P.alpha_pow[t];
-    const int64_t *arow = io.act + (valid ? e : N - 1) * M1;
-    // episode sink (kernels.hpp EpSink): the running return and the group's
-    // partials are loaded with the step's other loads
-    double *const ep_part = P.cm.ep_ret ? P.cm.ep_part + 4 * (e0 / WAVE) : nullptr;
-    EpPart epp;
-    double ep_r = 0.0;
-    if (ep_part) {
-        epp.load(ep_part);
-        ep_r = P.cm.ep_ret[valid ? e : N - 1];
-    }
+    TPROBE_ARGS(1, WAVE, (int)N + gla);
+    const int64_t *arow = act + (valid ? e : N - 1) * M1;
     int64_t req[M1], arr[M1], I[M1], B[M1 + 1];
     // DEC: this step's demand straight from the lookahead slot, so the dynamics
     // wave does not wait for the window wave's loads before its arithmetic
@@ -865,7 +920,7 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
 #pragma unroll
             for (int i = 0; i < M1; i++) wd[(r - RW) * M1 + i] = (uint32_t)(r + i);
 #else
-            const uint32_t *src = P.alog32 + wrow(r < rmax ? r : rmax);
+            const uint32_t *src = a32 + wrow(r < rmax ? r : rmax);
 #pragma unroll
             for (int i = 0; i < M1; i++) wd[(r - RW) * M1 + i] = src[i];
 #endif
@@ -875,15 +930,25 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
     for (int i = 0; i < M1; i++) req[i] = arow[i];
 #pragma unroll
     for (int i = 0; i < M1; i++) {                                  // arrivals R[t-L_i] (:271-277)
-        const int L = P.L[i];
-        const int row = L > 0 ? P.ring_off[i] + (int)((uint32_t)t % (uint32_t)L) : 0;
-        arr[i] = P.Rring[(int64_t)row * S + e];
-        if (!(L > 0 && t >= L)) arr[i] = 0;
+        const int row = arrival_row(i);
+        const bool none = row < 0;                                  // (then any valid row, unused)
+        arr[i] = Rr[(int64_t)(none ? 0 : row) * S + e];
+        if (none) arr[i] = 0;
     }
 #pragma unroll
-    for (int i = 0; i < M1; i++) I[i] = P.I[i * S + e];
+    for (int i = 0; i < M1; i++) I[i] = Ip[i * S + e];
 #pragma unroll
-    for (int q = 0; q <= M1; q++) B[q] = BACKLOG ? P.B[q * S + e] : 0;
+    for (int q = 0; q <= M1; q++) B[q] = BACKLOG ? Bp[q * S + e] : 0;
+    // episode sink (kernels.hpp EpSink): the running return and the group's
+    // partials are loaded with the step's other loads (behind them: the sink's
+    // pointers are P fields)
+    double *const ep_part = P.cm.ep_ret ? P.cm.ep_part + 4 * (e0 / WAVE) : nullptr;
+    EpPart epp;
+    double ep_r = 0.0;
+    if (ep_part) {
+        epp.load(ep_part);
+        ep_r = P.cm.ep_ret[valid ? e : N - 1];
+    }
     int64_t ordreq[M1], R[M1], Icur[M1];
 #pragma unroll
     for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;  // :250
@@ -975,23 +1040,23 @@ im_split_kernel(ImParams P, int t, StepIO<int64_t, int64_t> io, int cur, int la0
         im_flush_pending<M1>(P, pend, e);
         out_store(io.rew + e, reward);
         out_store(io.term + e, (uint8_t)0);
-        out_store(io.trunc + e, (uint8_t)(t1 >= P.periods ? 1 : 0));   // :350
+        out_store(io.trunc + e, (uint8_t)(trunc ? 1 : 0));   // :350
         if (P.cm.info_demand) P.cm.info_demand[e] = d;
 #pragma unroll
-        for (int i = 0; i < M1; i++) st_store(P.I + i * S + e, Icur[i]);   // :326
+        for (int i = 0; i < M1; i++) st_store(Ip + i * S + e, Icur[i]);   // :326
         if (BACKLOG) {
 #pragma unroll
-            for (int q = 0; q <= M1; q++) st_store(P.B + q * S + e, U[q]);   // :307-312
+            for (int q = 0; q <= M1; q++) st_store(Bp + q * S + e, U[q]);   // :307-312
         }
     }
     if (ep_part) {   // after the stores: the butterfly runs while they drain
         EpLane a;
         if (valid) {
             a.r = ep_r;
-            a.add(reward, t1 >= P.periods);               // terminated is always False (:350)
+            a.add(reward, trunc != 0);                    // terminated is always False (:350)
             P.cm.ep_ret[e] = a.r;
         }
-        epp.flush(ep_part, a, t1 >= P.periods, lane);
+        epp.flush(ep_part, a, trunc != 0, lane);
     }
     TWAIT();
     TPROBE_AT(4, WAVE);   // the dynamics wave's exit (probe 3: its entry)
@@ -1875,9 +1940,45 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
     return hipGetLastError();
 }
 
+// im_split_kernel's launch-time values (see the kernel's argument list): the
+// host knows t, so every wave need not derive them
+struct ImSplitArgs {
+    int32_t n32;
+    uint32_t hw;     // ImHot word, or 0
+    uint64_t *acur;  // the current lookahead slot, or null
+    double apow;     // alpha ** t, the very double of the device table
+    int n, nw, trunc;
+};
+inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M1, int t, int cur) {
+    ImSplitArgs a{};
+    a.n32 = (int32_t)q.cm.N;
+    a.acur = q.ahead ? q.ahead + (int64_t)cur * 4 * pad_n(q.cm.N) : nullptr;
+    a.apow = ap_host[t];
+    const int D = q.lt_max, t1 = t + 1;
+    a.n = D > 0 ? (t1 < D ? t1 : D) : 0;                      // window rows incl. the newest
+    a.nw = a.n > 0 ? (a.n - 1) * M1 : 0;
+    a.trunc = t1 >= q.periods ? 1 : 0;                        // :350
+    int sumL = 0;
+    for (int i = 0; i < M1; i++) sumL += q.L[i];
+    if (M1 == ImHot::M1 && D <= 15 && sumL <= ImHot::NOARR) {
+        const uint32_t slot0 = D > 0 ? (uint32_t)(t1 - a.n) % (uint32_t)D : 0;
+        const uint32_t rmax = a.nw > 0 ? (uint32_t)(a.nw / M1 - 1) : 0;
+        uint32_t w = (1u << 31) | slot0 | (rmax << 4) | ((uint32_t)D << 8);
+        for (int i = 0; i < M1; i++) {
+            const int L = q.L[i];
+            const uint32_t row = (L > 0 && t >= L) ? (uint32_t)(q.ring_off[i] + t % L) : (uint32_t)ImHot::NOARR;
+            w |= row << (12 + 6 * i);
+        }
+        a.hw = w;
+    }
+    return a;
+}
+// the arguments of a launch, in the kernel's order (q: its ImParams, ha: the above)
+#define IM_SPLIT_ARGS io.act, q.I, q.B, q.Rring, q.alog32, ha.acur, ha.n32, ha.hw, q, t_u, io, cur, ha.apow, ha.n, ha.nw, ha.trunc
+
 }  // namespace
 
-#define IM_DISPATCH(M1V, BL, LAUNCH)                                   \
+#define IM_DISPATCH(M1V, BL, LAUNCH)                                  \
     switch (M1V) {                                                     \
         case 1: if (BL) LAUNCH(1, true); else LAUNCH(1, false); break; \
         case 2: if (BL) LAUNCH(2, true); else LAUNCH(2, false); break; \
@@ -1893,7 +1994,7 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
 #ifdef INVSIM_IM_FAST_TU
 // invmgmt_ph.hip: this file compiled a second time for the fast-stream run
 // kernels (a TU of their own, so the two instantiation sets compile in parallel)
-hipError_t im_run_launch_ph(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
+hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
     sunk = im_sink_noop(p, t_u, pol, io);
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
@@ -1910,17 +2011,17 @@ hipError_t im_run_launch_ph(const ImParams &p, int M1, bool backlog, int t_u, co
         const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;
         const dim3 grid2(grid.x + gla), block2(2 * WAVE);
         const int cur = slot;
-        // the lookahead workgroups are the first gla of the grid; la0 stays a kernel
-        // argument because folding it into the kernel changed its register allocation
-        const int la0 = 0;
+        // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
+        if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
+        const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);  \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, PhiloxGen>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);     \
+            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
         } else {                                                                                        \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla); \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, PhiloxGen>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);    \
+            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
         }                                                                                               \
     } while (0)
         IM_DISPATCH(M1, backlog, S_)
@@ -1964,7 +2065,7 @@ hipError_t im_run_launch_ph(const ImParams &p, int M1, bool backlog, int t_u, co
 
 INVSIM_PTRS_STATS_TU(im_ph)
 #else
-hipError_t im_run_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
+hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                          const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
     sunk = im_sink_noop(p, t_u, pol, io);
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
@@ -1974,7 +2075,7 @@ hipError_t im_run_launch(const ImParams &p, int M1, bool backlog, int t_u, const
     const PolicyIO &pv = pol ? *pol : none;
     const bool npd = p.dist >= 2 && p.dist <= 4;
     const bool ph = p.cm.philox != 0;       // fast stream: invmgmt_ph.hip (split / rollout / run kernels, no lookahead)
-    if (ph) return im_run_launch_ph(p, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);   // (a cache is the fast stream's)
+    if (ph) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);   // (a cache is the fast stream's)
     if (im_split_applies(p, t_u, pol, io)) {
         const size_t lds2 = lds + WAVE * sizeof(int64_t);
         const dim3 block2(2 * WAVE);
@@ -1989,17 +2090,17 @@ hipError_t im_run_launch(const ImParams &p, int M1, bool backlog, int t_u, const
         const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;   // lookahead workgroups
         const dim3 grid2(grid.x + gla);
         const int cur = slot;
-        // the lookahead workgroups are the first gla of the grid; la0 stays a kernel
-        // argument because folding it into the kernel changed its register allocation
-        const int la0 = 0;
+        // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
+        if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
+        const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);  \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);     \
+            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
         } else {                                                                                        \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla); \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false>), grid2, block2, lds2, s, q, t_u, io, cur, la0, gla);    \
+            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
         }                                                                                               \
     } while (0)
         IM_DISPATCH(M1, backlog, S_)
@@ -2078,6 +2179,9 @@ INVSIM_PTRS_STATS_TU(im)
 #if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU)
 extern "C" int invsim_debug_timing(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbuf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
+}
+extern "C" int invsim_debug_timing_args(void *dst, int64_t bytes) {
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_targ), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }
 extern "C" int invsim_debug_timing_bar(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbar), (size_t)bytes, 0, hipMemcpyDeviceToHost);

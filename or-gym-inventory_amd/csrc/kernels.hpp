@@ -15,6 +15,14 @@ namespace invsim {
 
 enum { AR_NEXT_STEP = 0, AR_SAME_STEP = 1, AR_DISABLED = 2 };
 
+// The SoA row stride of a handle of n envs (Common::Npad): n rounded up to 256,
+// at least 256.  The one statement of the rule: the host sizes the arena with
+// it, and a kernel that is handed only N (im_split_kernel's leading scalar
+// arguments) derives the stride from it.
+__host__ __device__ constexpr int64_t pad_n(int64_t n) {
+    return n <= 256 ? 256 : (n + 255) / 256 * 256;
+}
+
 // Profiling-only per-wave phase timestamps (`make timing`; never in the shipped
 // library): lane 0 of wave b writes s_memrealtime (100 MHz) for probe i to
 // g_tbuf[b][i]; probe 7 holds (XCC_ID << 32) | HW_ID.
@@ -316,6 +324,29 @@ struct ImParams {
     uint64_t *ahead;
 };
 
+// im_split_kernel's leading scalar arguments (kernarg preload: the first
+// IM_HOT_DWORDS dwords of the argument segment arrive in SGPRs): six pointers,
+// N, and this packed word of what the host knows at launch about a 3-stage
+// (M1 = 3) step at period t:
+//   bits  0-3   slot0  ring slot of the observation window's first row
+//   bits  4-7   rmax   last window row that holds a logged order
+//   bits  8-11  D      window depth (lt_max <= 15)
+//   bits 12-29  three 6-bit R-ring rows of the stages' arrivals,
+//               ring_off[i] + t mod L[i] (<= 62), or NOARR: nothing arrives
+//   bit  31     packed
+// A spec that does not fit (another stage count, lt_max > 15, sum L > 63)
+// gets 0, and the kernel derives the same values from ImParams.
+constexpr int IM_HOT_DWORDS = 14;   // = csrc/Makefile -amdgpu-kernarg-preload-count
+struct ImHot {
+    static constexpr int M1 = 3;
+    static constexpr int NOARR = 63;
+    __host__ __device__ static constexpr bool packed(uint32_t w) { return (w >> 31) != 0; }
+    __host__ __device__ static constexpr int slot0(uint32_t w) { return (int)(w & 15u); }
+    __host__ __device__ static constexpr int rmax(uint32_t w) { return (int)((w >> 4) & 15u); }
+    __host__ __device__ static constexpr int depth(uint32_t w) { return (int)((w >> 8) & 15u); }
+    __host__ __device__ static constexpr int row(uint32_t w, int i) { return (int)((w >> (12 + 6 * i)) & 63u); }
+};
+
 // ---------------------------------------------------------------- NetInvMgmt
 struct NetParams {
     Common cm;
@@ -605,11 +636,13 @@ hipError_t im_reset_launch(const ImParams &p, int M1, bool backlog, const uint8_
 // slot (updated) does now
 // sunk: out = the launched kernel folded its rows into the episode sink
 // (Common::ep_ret), or had nothing to fold; else the caller folds the outputs
-hipError_t im_run_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
+// ap_host: the host's copy of the alpha_pow table (the split step kernel takes
+// alpha ** t by value)
+hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                          const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s);
 // the fast-stream (cm.philox) kernels, invmgmt_ph.hip; ahead / slot: the
 // fast stream's demand-only lookahead cache (never committed: it holds no state)
-hipError_t im_run_launch_ph(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
+hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s);
 // cm.rng <- the committed generator state held by the lookahead cache (whose
 // current slot is `slot`); needed before anything reads cm.rng while it is valid

@@ -7,7 +7,11 @@ waves (profiling only; needs the TIMING build, csrc `make timing`).
 Probes (s_memrealtime, 100 MHz): 0 workgroup entry (thread 0); lookahead
 1 loads + RHS table in LDS, 2 demand drawn, 5 exit; step 3 / 4 dynamics wave
 entry / exit, 1 its loads in and d handed over, 2 its step computed (tile
-complete), 6 / 5 window wave: rows landed / exit.
+complete), 6 / 5 window wave: rows landed / exit.  A second buffer
+(invsim_debug_timing_args) holds, per workgroup, when the window wave (or the
+lookahead workgroup) and the dynamics wave first held an argument-derived
+scalar: "entry -> args in" is the wait on the kernel-argument loads plus the
+probe's own cost, "args in -> loads in" the rest of the wave's first segment.
 """
 import ctypes as C
 import os
@@ -36,7 +40,11 @@ def main():
     buf = np.zeros((8192, 8), dtype=np.uint64)
     rc = _capi.lib().invsim_debug_timing(buf.ctypes.data_as(C.c_void_p), C.c_int64(buf.nbytes))
     assert rc == 0, rc
+    abuf = np.zeros((8192, 2), dtype=np.uint64)
+    rc = _capi.lib().invsim_debug_timing_args(abuf.ctypes.data_as(C.c_void_p), C.c_int64(abuf.nbytes))
+    assert rc == 0, rc
     b = buf.astype(np.int64)
+    ab = abuf.astype(np.int64)
     gla = (n + 127) // 128
     nst = (n + 63) // 64
     tot = gla + nst
@@ -45,13 +53,20 @@ def main():
     fmt = lambda x: " ".join(f"{v * 10.0:7.0f}" for v in np.percentile(x, pct))
     print("ns percentiles          p0      p10     p50     p90     max")
     la, st = b[:gla], b[gla:tot]
+    ala, ast = ab[:gla], ab[gla:tot]
     print(f"-- lookahead: {gla} workgroups")
     print("  entry             " + fmt(la[:, 0] - t0))
+    print("  entry->args in    " + fmt(ala[:, 0] - la[:, 0]))
+    print("  args in->loaded   " + fmt(la[:, 1] - ala[:, 0]))
     print("  entry->loaded     " + fmt(la[:, 1] - la[:, 0]))
     print("  draw              " + fmt(la[:, 2] - la[:, 1]))
     print("  exit              " + fmt(la[:, 5] - t0))
     print(f"-- step: {nst} workgroups")
     print("  entry             " + fmt(st[:, 0] - t0))
+    print("  window: entry->args in    " + fmt(ast[:, 0] - st[:, 0]))
+    print("  window: args in->rows in  " + fmt(st[:, 6] - ast[:, 0]))
+    print("  dynamics: entry->args in  " + fmt(ast[:, 1] - st[:, 0]))
+    print("  dynamics: args in->loads in " + fmt(st[:, 1] - ast[:, 1]))
     print("  window exit       " + fmt(st[:, 5] - t0))
     print("  window rows in    " + fmt(st[:, 6] - t0))
     print("  dynamics entry    " + fmt(st[:, 3] - t0))
