@@ -57,6 +57,10 @@ class _Oracle:
         self.t += 1
         return o, r, tr
 
+    def reset(self):
+        self.t = 0
+        return self.orc.reset()
+
     def check(self, out, act, where):
         o, r, tr = self.row(act)
         assert _eq_bits(_np(out[0]), o), f"obs vs oracle {where}"
@@ -69,17 +73,31 @@ class _Oracle:
         assert np.array_equal(got, self.orc.rng_state()), "PCG64 state vs oracle"
 
 
+UNKNOWN = 0xFFFFFFFF    # low word of position() once the periods come from the device (no lock-step)
+
+
+def _lock_step(env):
+    return env.position() & UNKNOWN != UNKNOWN
+
+
 def _drive(envs, acts, orc=None, rollout_at=None, state_at=None):
     """Step every env of `envs` through acts [K][n][m1] (one invsim_step each; at
     call rollout_at one invsim_rollout of three rows instead; before call
-    state_at a get_state / set_state round trip), comparing every row with
-    envs[0]'s and with the oracle's, then the final blobs."""
+    state_at a get_state / set_state round trip, which ends lock-step: from
+    there on the per-env one-wave kernel runs on every handle), comparing every
+    row with envs[0]'s and with the oracle's, then the final blobs.  Up to
+    state_at every call is asserted to be made in lock-step."""
     K, k = acts.shape[0], 0
     dev = torch.from_numpy(acts).to(envs[0].device)
+    locked = True
     while k < K:
         if k == state_at:
             for env in envs:
                 env.set_state(env.get_state().clone())
+                assert not _lock_step(env)
+            locked = False
+        if locked:
+            assert all(_lock_step(env) for env in envs), f"lock-step before call {k}"
         if k == rollout_at:
             outs = [tuple(x.clone() for x in env.rollout(dev[k:k + 3])) for env in envs]
             for j in range(3):
@@ -111,10 +129,14 @@ def _acts(seed, K, n, m1, c):
 @gpu_test
 @pytest.mark.parametrize("cls_name", ["InvManagementBacklogEnv", "InvManagementLostSalesEnv"])
 def test_base_case(gpu, oracle, monkeypatch, cls_name):
-    """63 steps under NEXT_STEP (two episodes, two reset steps, period 0 of the
-    third): the window grows while t < D and the ring wraps; the first step after
-    seeding, after a mid-run set_state (before call 7) and after an interleaved
-    three-row rollout (calls 40-42) takes the inline-draw variant."""
+    """63 steps under NEXT_STEP (two episodes, two reset steps, the first periods
+    of the third), all in lock-step: the window grows while t < D and the ring
+    wraps; the first step after seeding and after an interleaved three-row
+    rollout (calls 40-42) takes the inline-draw variant.  Then a get_state /
+    set_state round trip: the periods now come from the blob, so two steps run
+    on the per-env one-wave kernel of both handles; an unmasked reset restores
+    lock-step, and the first of six more split steps is the inline-draw
+    variant after a set_state."""
     import invsim
     n, seed = 197, 910
     envs = _pair(monkeypatch, lambda: getattr(invsim, cls_name)(n, device=gpu))
@@ -122,7 +144,15 @@ def test_base_case(gpu, oracle, monkeypatch, cls_name):
     for env in envs:
         obs, _ = env.reset(seed=seed)
         assert _eq_bits(_np(obs), orc.obs0)
-    _drive(envs, _acts(1, 66, n, 3, [100, 200, 230]), orc, rollout_at=40, state_at=7)
+    acts = _acts(1, 74, n, 3, [100, 200, 230])
+    _drive(envs, acts[:66], orc, rollout_at=40)
+    _drive(envs, acts[66:68], orc, state_at=0)
+    e_obs = orc.reset()
+    for env in envs:
+        obs, _ = env.reset()
+        assert _lock_step(env)
+        assert _eq_bits(_np(obs), e_obs), "reset obs after the round trip"
+    _drive(envs, acts[68:], orc)
 
 
 _M1_1 = dict(I0=(60,), p=14, r=(10, 6), k=(0.2, 0.1), h=(0.1,), c=(90,), L=(4,))
