@@ -34,16 +34,23 @@ __device__ uint64_t g_tbuf[TB_WAVES * TB_PROBES];
 // im_split_kernel: the time at which a wave holds its first kernel-argument
 // values, g_targ[workgroup][0 window wave / lookahead workgroup, 1 dynamics
 // wave].  `dep` is an argument-derived scalar: the empty asm needs it in an
-// SGPR, so the timestamp follows the wait on the argument loads (if any)
-__device__ uint64_t g_targ[TB_WAVES * 2];
+// SGPR, so the timestamp follows the wait on the argument loads (if any).
+// g_targ[workgroup][2]: when the dynamics wave had issued its state stores.
+__device__ uint64_t g_targ[TB_WAVES * 3];
 #define TPROBE_ARGS(col, tid, dep)                                                             \
     do {                                                                                       \
         asm volatile("" ::"s"(dep));                                                           \
         if (threadIdx.x == (tid) && blockIdx.x < TB_WAVES)                                     \
-            g_targ[blockIdx.x * 2 + (col)] = __builtin_amdgcn_s_memrealtime();                 \
+            g_targ[blockIdx.x * 3 + (col)] = __builtin_amdgcn_s_memrealtime();                 \
+    } while (0)
+#define TPROBE_STORES(tid)                                                                     \
+    do {                                                                                       \
+        if (threadIdx.x == (tid) && blockIdx.x < TB_WAVES)                                     \
+            g_targ[blockIdx.x * 3 + 2] = __builtin_amdgcn_s_memrealtime();                     \
     } while (0)
 #else
 #define TPROBE_ARGS(col, tid, dep) do {} while (0)
+#define TPROBE_STORES(tid) do {} while (0)
 #endif
 
 // obs-window entries per lane kept in registers: the (lt_max - 1) * M1 entries
@@ -75,10 +82,31 @@ __device__ __forceinline__ int64_t min_via_f64(int64_t a, int64_t sup) {
     return (int64_t)((x <= y) ? x : y);
 }
 
-// The step's global stores, issued after the obs tile store: gfx9 VMEM stores
-// read their data VGPRs late and vmcnt also counts stores, so a store issued
-// before the tile copy makes every later overwrite of its data registers wait
-// for the store to complete.
+// The step's state stores (ring rows, action_log row, I, B; ImPending holds the
+// first two).  vmcnt counts stores as well as loads on gfx9, so a wait for a
+// load issued after a store also waits for that store; the multi-step kernels
+// issue the state stores after the obs tile store, where no load follows.
+// im_split_kernel's EARLY instantiation (launches of more than
+// IM_EARLY_STORES_MIN_N envs) issues them (im_store_rows, as im_flush_pending) as
+// soon as the integer dynamics are done, in front of the tile barrier, where
+// it would otherwise wait for the window wave, and the f64 reward chain, which
+// the tile does not need, runs behind the tile copy.  In the generated gfx950
+// code no vmcnt wait stands between the first of those stores and the last
+// tile store, except inside the exec-guarded branch that fetches a wide
+// entry; the compiler reuses the stores' address and data registers right
+// after them with no wait.  Two properties make the early stores safe, and a
+// change to the kernel has to keep them:
+//   - the window rows whose values are used are ring slots (t+1-n .. t-1) mod D
+//     and the action_log row written is slot t mod D, never among them.  The
+//     straight-line loads of rows past the last logged one (clamped to rmax:
+//     t = 0, or D = 1) may touch slot t mod D, but their values are discarded
+//     (entries >= nw are never read from the registers, nor tested for
+//     IM_WIDE), whatever they return;
+//   - Rring slot t mod L_i is read (this period's arrival) and written (R[t])
+//     by the same lane of the same wave, and the load has returned before the
+//     dynamics that produce R[t] run (the wave waits for I and B, loaded
+//     after the arrivals, and gfx9 loads return in order).  I and B rows
+//     likewise: one lane reads, then writes.
 template <int M1>
 struct ImPending {
     int64_t R[M1], req[M1];
@@ -299,6 +327,31 @@ __device__ __forceinline__ bool im_step_regs(const ImParams &P, int64_t e, bool 
     for (int i = 0; i < M1; i++) pend.req[i] = req[i];              // action_log[t] (:268)
     TPROBE(3);
     return t1 >= P.periods;                                         // :350
+}
+
+// im_flush_pending's stores with the rows given (im_split_kernel's EARLY
+// order works them out during its load phase): R[i] to ring row srow[i] (< 0:
+// no ring store, L_i = 0), the requested orders to action_log slot wslot (with
+// the int64 side ring for entries >= 2^32 - 1).  im_flush_pending keeps its
+// own body: built on this helper, the run and rollout kernels that use it came
+// out with other register and spill figures.  A change to the ring layout has
+// to reach both.
+template <int M1>
+__device__ __forceinline__ void im_store_rows(int64_t *Rring, uint32_t *alog32, int64_t *alog, int64_t S, int D,
+                                              const int (&srow)[M1], int wslot, const int64_t (&R)[M1],
+                                              const int64_t (&req)[M1], int64_t e) {
+#pragma unroll
+    for (int i = 0; i < M1; i++)
+        if (srow[i] >= 0) st_store(Rring + (int64_t)srow[i] * S + e, R[i]);
+    if (D > 0) {
+#pragma unroll
+        for (int i = 0; i < M1; i++) {
+            const int64_t idx = ((int64_t)wslot * S + e) * M1 + i;
+            const bool wide = req[i] >= (int64_t)IM_WIDE;
+            st_store(alog32 + idx, wide ? IM_WIDE : (uint32_t)req[i]);
+            if (wide) st_store(alog + idx, req[i]);
+        }
+    }
 }
 
 template <int M1>
@@ -657,7 +710,19 @@ __device__ __forceinline__ void wg_lds_sync() {
 constexpr int im_split_waves(int m1, bool npd, bool ahead, bool counter) {
     return (m1 == 2 && npd && ahead && !counter) ? 5 : 1;
 }
-template <int M1, bool BACKLOG, bool NPD, bool AHEAD, class RG = Pcg>
+// EARLY (im_split_kernel): the dynamics wave issues its state stores in front
+// of the tile barrier and computes the reward behind the tile copy.  The host
+// picks that instantiation for lookahead steps of more than this many envs.
+// With more than two step workgroups per CU (256 CUs x 2 x 64 envs) the launch
+// ends at the plain-store rate and the dynamics wave idles at the barrier, so
+// stores issued there are free; with two or fewer the step is one wave's
+// load -> compute -> store chain, nothing waits at the barrier, and stores in
+// front of it only delay the window wave's tile half (+6 % at 32 768 envs when
+// tried).  !EARLY is the order the kernel always had.  The inline-draw step
+// (!AHEAD, once after a seed or a set_state) keeps it at every size.
+// profiles/early_stores/table.md
+constexpr int IM_EARLY_STORES_MIN_N = 32768;
+template <int M1, bool BACKLOG, bool NPD, bool AHEAD, class RG = Pcg, bool EARLY = false>
 __global__ void __launch_bounds__(2 * WAVE)
     __attribute__((amdgpu_waves_per_eu(im_split_waves(M1, NPD, AHEAD, RG::kCounter))))
 im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr, const uint32_t *a32, uint64_t *Acur,
@@ -949,6 +1014,25 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
         epp.load(ep_part);
         ep_r = P.cm.ep_ret[valid ? e : N - 1];
     }
+    // EARLY: where this step's ring and action_log stores go (im_store_rows),
+    // worked out while the loads are in flight so that no division stands
+    // between the dynamics and the stores: stage i's R[t] goes to ring slot
+    // t mod L_i, the row its arrival was read from (t < L_i: slot t, nothing
+    // arrived yet; L_i = 0: no ring store), and action_log[t] to slot t mod D,
+    // the one after the window's n - 1 logged rows
+    int srow[M1];
+    int wslot = 0;
+    int64_t *alogw = nullptr;
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int i = 0; i < M1; i++) {
+            const int row = arrival_row(i);
+            srow[i] = row >= 0 ? row : P.L[i] > 0 ? P.ring_off[i] + t : -1;
+        }
+        wslot = slot0 + n - 1;
+        wslot = wslot >= D ? wslot - D : wslot;
+        alogw = P.alog;
+    }
     int64_t ordreq[M1], R[M1], Icur[M1];
 #pragma unroll
     for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;  // :250
@@ -977,76 +1061,145 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
     Icur[0] = wrap_sub(Icur[0], s0);
     Sv[0] = s0;
     U[0] = wrap_sub(dfill, s0);                                     // :303
-    double term[M1 + 1];                                            // :315-321
+    // the reward (:315-322); nothing in the obs tile needs it
+    double profit = 0.0, reward = 0.0;
+    auto reward_chain = [&]() {
+        double term[M1 + 1];
 #pragma unroll
-    for (int q = 0; q <= M1; q++) {
-        const double Sj = (double)Sv[q];
-        const int64_t inv = (q < M1) ? Icur[q] : 0;
-        const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
-        term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
-    }
-    const double profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
-    const double reward = apow * profit;                            // :322
-#pragma unroll
-    for (int i = 0; i < M1; i++) trow[i] = Icur[i];                 // obs (:354-391)
-    if (D > 0) {
-#pragma unroll
-        for (int i = 0; i < M1; i++) w[(n - 1) * M1 + i] = req[i];  // newest row last (:380)
-    }
-    if (wsplit) {   // its window rows (an entry >= 2^32 - 1 from the int64 side ring)
-#pragma unroll
-        for (int j = 0; j < (RWN - RW) * M1; j++) {
-            const int u = RW * M1 + j;
-            if (u < nw) w[u] = wd[j] == IM_WIDE ? P.alog[wrow(u / M1) + u % M1] : (int64_t)wd[j];
+        for (int q = 0; q <= M1; q++) {
+            const double Sj = (double)Sv[q];
+            const int64_t inv = (q < M1) ? Icur[q] : 0;
+            const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
+            term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
         }
-    }
-    wg_lds_sync();   // tile complete
-    TPROBE_AT(2, WAVE);   // the dynamics wave: step computed, stores next
-    {
+        profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
+        reward = apow * profit;                                     // :322
+    };
+    auto info_record = [&]() {   // step info (:334-345), as im_step_regs
+        if (!P.cm.info_rec) return;
+        constexpr int W = 2 * (M1 + 1) + 5;
+        int64_t *rr = (int64_t *)P.cm.info_rec + e * W;
+#pragma unroll
+        for (int q = 0; q <= M1; q++) {
+            rr[q] = Sv[q];
+            rr[M1 + 1 + q] = U[q];
+        }
+        const double rev = np_sum<double>(M1 + 1, [&](int q) { return P.up[q] * (double)Sv[q]; });
+        const double pro = np_sum<double>(M1 + 1, [&](int q) { return P.uc[q] * (double)Sv[q]; });
+        const double hol = np_sum<double>(M1 + 1, [&](int q) {
+            const int64_t inv = (q < M1) ? Icur[q] : 0;
+            return P.hc[q] * (double)(inv > 0 ? inv : 0);
+        });
+        const double pen = np_sum<double>(M1 + 1, [&](int q) { return P.kc[q] * (double)U[q]; });
+        rr[2 * (M1 + 1) + 0] = __double_as_longlong(profit);
+        rr[2 * (M1 + 1) + 1] = __double_as_longlong(rev);
+        rr[2 * (M1 + 1) + 2] = __double_as_longlong(pro);
+        rr[2 * (M1 + 1) + 3] = __double_as_longlong(hol);
+        rr[2 * (M1 + 1) + 4] = __double_as_longlong(pen);
+    };
+    auto tile_half = [&]() {
         const int64_t h = thalf < tcount ? thalf : tcount;
         if (tcount > h)
             store_tile<(M1 * 11 * WAVE * 8 / 2 + 16 * WAVE - 1) / (16 * WAVE)>(im_tile + h, io.obs + e0 * O + h,
                                                                               tcount - h, lane);
-    }
-    if (valid) {
-        if (P.cm.info_rec) {   // step info (:334-345), as im_step_regs
-            constexpr int W = 2 * (M1 + 1) + 5;
-            int64_t *rr = (int64_t *)P.cm.info_rec + e * W;
+    };
+    if constexpr (EARLY) {
+        // The state stores in front of the tile barrier (see ImPending): each is
+        // whole 128-byte lines from one wave instruction, and the wave would
+        // otherwise idle here until the window wave's rows have landed.
+        // Nothing between here and the tile copy writes a register they read.
+        if (valid) {
+            im_store_rows<M1>(const_cast<int64_t *>(Rr), const_cast<uint32_t *>(a32), alogw, S, D, srow, wslot, R, req,
+                              e);   // Rr, a32: P.Rring, P.alog32
 #pragma unroll
-            for (int q = 0; q <= M1; q++) {
-                rr[q] = Sv[q];
-                rr[M1 + 1 + q] = U[q];
+            for (int i = 0; i < M1; i++) st_store(Ip + i * S + e, Icur[i]);   // :326
+            if (BACKLOG) {
+#pragma unroll
+                for (int q = 0; q <= M1; q++) st_store(Bp + q * S + e, U[q]);   // :307-312
             }
-            const double rev = np_sum<double>(M1 + 1, [&](int q) { return P.up[q] * (double)Sv[q]; });
-            const double pro = np_sum<double>(M1 + 1, [&](int q) { return P.uc[q] * (double)Sv[q]; });
-            const double hol = np_sum<double>(M1 + 1, [&](int q) {
-                const int64_t inv = (q < M1) ? Icur[q] : 0;
-                return P.hc[q] * (double)(inv > 0 ? inv : 0);
-            });
-            const double pen = np_sum<double>(M1 + 1, [&](int q) { return P.kc[q] * (double)U[q]; });
-            rr[2 * (M1 + 1) + 0] = __double_as_longlong(profit);
-            rr[2 * (M1 + 1) + 1] = __double_as_longlong(rev);
-            rr[2 * (M1 + 1) + 2] = __double_as_longlong(pro);
-            rr[2 * (M1 + 1) + 3] = __double_as_longlong(hol);
-            rr[2 * (M1 + 1) + 4] = __double_as_longlong(pen);
+            out_store(io.term + e, (uint8_t)0);
+            out_store(io.trunc + e, (uint8_t)(trunc ? 1 : 0));   // :350
         }
-        ImPending<M1> pend;
+        TPROBE_STORES(WAVE);   // the dynamics wave: state stores issued
 #pragma unroll
-        for (int i = 0; i < M1; i++) {
-            pend.R[i] = R[i];                                           // ring slot t mod L <- R[t] (:267)
-            pend.req[i] = req[i];                                       // action_log[t] (:268)
+        for (int i = 0; i < M1; i++) trow[i] = Icur[i];                 // obs (:354-391)
+        if (D > 0) {
+#pragma unroll
+            for (int i = 0; i < M1; i++) w[(n - 1) * M1 + i] = req[i];  // newest row last (:380)
         }
-        pend.t = t;
-        im_flush_pending<M1>(P, pend, e);
-        out_store(io.rew + e, reward);
-        out_store(io.term + e, (uint8_t)0);
-        out_store(io.trunc + e, (uint8_t)(trunc ? 1 : 0));   // :350
-        if (P.cm.info_demand) P.cm.info_demand[e] = d;
+        if (wsplit) {   // its window rows
+            bool wide = false;
 #pragma unroll
-        for (int i = 0; i < M1; i++) st_store(Ip + i * S + e, Icur[i]);   // :326
-        if (BACKLOG) {
+            for (int j = 0; j < (RWN - RW) * M1; j++) {
+                const int u = RW * M1 + j;
+                if (u < nw) w[u] = (int64_t)wd[j];
+                wide |= (u < nw) && wd[j] == IM_WIDE;
+            }
+            // an entry >= 2^32 - 1 from the int64 side ring: in a branch of its
+            // own, as in the window wave, so that the wait for these loads (a
+            // vmcnt wait, which would cover the state stores above) is only
+            // reached by a wave that holds such an entry
+            if (wide) {
 #pragma unroll
-            for (int q = 0; q <= M1; q++) st_store(Bp + q * S + e, U[q]);   // :307-312
+                for (int j = 0; j < (RWN - RW) * M1; j++) {
+                    const int u = RW * M1 + j;
+                    if (u < nw && wd[j] == IM_WIDE) w[u] = alogw[wrow(u / M1) + u % M1];
+                }
+            }
+        }
+        wg_lds_sync();   // tile complete
+        TPROBE_AT(2, WAVE);   // the dynamics wave: past the tile barrier, its tile half next
+        tile_half();
+        // the reward behind the tile copy: in front of the barrier the f64 chain
+        // would hold up the window wave's tile half as well (the dynamics wave is
+        // the later of the two there once it issues its state stores first)
+        reward_chain();
+        if (valid) {
+            out_store(io.rew + e, reward);
+            info_record();
+            if (P.cm.info_demand) P.cm.info_demand[e] = d;
+        }
+    } else {
+        // launches of at most IM_EARLY_STORES_MIN_N envs: the state stores after
+        // the tile store (see ImPending)
+        reward_chain();
+        TPROBE_STORES(WAVE);   // (the reward computed)
+#pragma unroll
+        for (int i = 0; i < M1; i++) trow[i] = Icur[i];                 // obs (:354-391)
+        if (D > 0) {
+#pragma unroll
+            for (int i = 0; i < M1; i++) w[(n - 1) * M1 + i] = req[i];  // newest row last (:380)
+        }
+        if (wsplit) {   // its window rows (an entry >= 2^32 - 1 from the int64 side ring)
+#pragma unroll
+            for (int j = 0; j < (RWN - RW) * M1; j++) {
+                const int u = RW * M1 + j;
+                if (u < nw) w[u] = wd[j] == IM_WIDE ? P.alog[wrow(u / M1) + u % M1] : (int64_t)wd[j];
+            }
+        }
+        wg_lds_sync();   // tile complete
+        TPROBE_AT(2, WAVE);   // the dynamics wave: step computed, stores next
+        tile_half();
+        if (valid) {
+            info_record();
+            ImPending<M1> pend;
+#pragma unroll
+            for (int i = 0; i < M1; i++) {
+                pend.R[i] = R[i];                                           // ring slot t mod L <- R[t] (:267)
+                pend.req[i] = req[i];                                       // action_log[t] (:268)
+            }
+            pend.t = t;
+            im_flush_pending<M1>(P, pend, e);
+            out_store(io.rew + e, reward);
+            out_store(io.term + e, (uint8_t)0);
+            out_store(io.trunc + e, (uint8_t)(trunc ? 1 : 0));   // :350
+            if (P.cm.info_demand) P.cm.info_demand[e] = d;
+#pragma unroll
+            for (int i = 0; i < M1; i++) st_store(Ip + i * S + e, Icur[i]);   // :326
+            if (BACKLOG) {
+#pragma unroll
+                for (int q = 0; q <= M1; q++) st_store(Bp + q * S + e, U[q]);   // :307-312
+            }
         }
     }
     if (ep_part) {   // after the stores: the butterfly runs while they drain
@@ -2014,13 +2167,16 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
         // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
         if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
         const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
+        const bool early = p.cm.N > IM_EARLY_STORES_MIN_N;   // the EARLY instantiation (lookahead steps only)
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
             else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
         } else {                                                                                        \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
             else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
         }                                                                                               \
     } while (0)
@@ -2093,13 +2249,16 @@ hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool 
         // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
         if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
         const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
+        const bool early = p.cm.N > IM_EARLY_STORES_MIN_N;   // the EARLY instantiation (lookahead steps only)
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, Pcg, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
             else hipLaunchKernelGGL((im_split_kernel<M, B, true, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
         } else {                                                                                        \
-            if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, Pcg, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
             else hipLaunchKernelGGL((im_split_kernel<M, B, false, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
         }                                                                                               \
     } while (0)

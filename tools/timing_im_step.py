@@ -6,12 +6,16 @@ waves (profiling only; needs the TIMING build, csrc `make timing`).
 
 Probes (s_memrealtime, 100 MHz): 0 workgroup entry (thread 0); lookahead
 1 loads + RHS table in LDS, 2 demand drawn, 5 exit; step 3 / 4 dynamics wave
-entry / exit, 1 its loads in and d handed over, 2 its step computed (tile
-complete), 6 / 5 window wave: rows landed / exit.  A second buffer
-(invsim_debug_timing_args) holds, per workgroup, when the window wave (or the
-lookahead workgroup) and the dynamics wave first held an argument-derived
-scalar: "entry -> args in" is the wait on the kernel-argument loads plus the
-probe's own cost, "args in -> loads in" the rest of the wave's first segment.
+entry / exit, 1 its loads in and d handed over, 2 past the tile barrier (tile
+complete, its tile half next), 6 / 5 window wave: rows landed / exit.  A second
+buffer (invsim_debug_timing_args) holds, per workgroup, when the window wave
+(or the lookahead workgroup) and the dynamics wave first held an
+argument-derived scalar: "entry -> args in" is the wait on the kernel-argument
+loads plus the probe's own cost, "args in -> loads in" the rest of the wave's
+first segment; its third column is when the dynamics wave had issued its state
+stores (ring rows, action_log row, I, B, flags), in front of the tile barrier
+(more than 32 768 envs; at or below that the stores follow the tile copy and
+the column marks the end of the reward chain, which then runs in their place).
 """
 import ctypes as C
 import os
@@ -40,7 +44,7 @@ def main():
     buf = np.zeros((8192, 8), dtype=np.uint64)
     rc = _capi.lib().invsim_debug_timing(buf.ctypes.data_as(C.c_void_p), C.c_int64(buf.nbytes))
     assert rc == 0, rc
-    abuf = np.zeros((8192, 2), dtype=np.uint64)
+    abuf = np.zeros((8192, 3), dtype=np.uint64)
     rc = _capi.lib().invsim_debug_timing_args(abuf.ctypes.data_as(C.c_void_p), C.c_int64(abuf.nbytes))
     assert rc == 0, rc
     b = buf.astype(np.int64)
@@ -71,8 +75,11 @@ def main():
     print("  window rows in    " + fmt(st[:, 6] - t0))
     print("  dynamics entry    " + fmt(st[:, 3] - t0))
     print("  dynamics loads in " + fmt(st[:, 1] - t0))
+    print("  state stores issued " + fmt(ast[:, 2] - t0))
     print("  dynamics computed " + fmt(st[:, 2] - t0))
     print("  dynamics exit     " + fmt(st[:, 4] - t0))
+    print("  (stores issued - d in) " + fmt(ast[:, 2] - st[:, 1]))
+    print("  (computed - stores issued) " + fmt(st[:, 2] - ast[:, 2]))
     print("  (computed - d in) " + fmt(st[:, 2] - st[:, 1]))
     print("  (exit - computed) " + fmt(st[:, 4] - st[:, 2]))
     print("  (d in - entry)    " + fmt(st[:, 1] - st[:, 3]))
