@@ -82,6 +82,131 @@ __device__ __forceinline__ int64_t min_via_f64(int64_t a, int64_t sup) {
     return (int64_t)((x <= y) ? x : y);
 }
 
+// The period update (inventory_management.py:250-322), bit-exact, in the three
+// pieces the kernels need (im_split_kernel has a barrier between the first two
+// and runs the third behind its tile copy): im_orders, im_sales, im_profit.
+// im_step_regs and the dynamics waves of im_split_kernel, im_roll3_kernel and
+// im_roll3o_kernel all step through these.
+//
+// Orders (:250-277, :295-304): what does not depend on the demand.  req is
+// clamped in place; arrival(i) is R[t - L_i] (0 while t < L_i) and l0(i) says
+// whether L_i = 0 (the order arrives in its own period), each kernel's own way:
+// ring loads and P.L, or register windows and compile-time lead times.
+// Out: R, Icur (before sales), Sv[1..], U[1..].
+template <int M1, class ArrF, class L0F>
+__device__ __forceinline__ void im_orders(const ImParams &P, int64_t (&req)[M1], const int64_t (&I)[M1],
+                                          const int64_t (&B)[M1 + 1], ArrF arrival, L0F l0, int64_t (&R)[M1],
+                                          int64_t (&Icur)[M1], int64_t (&Sv)[M1 + 1], int64_t (&U)[M1 + 1]) {
+    int64_t ordreq[M1];
+#pragma unroll
+    for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;  // :250
+#pragma unroll
+    for (int i = 0; i < M1; i++) {
+        ordreq[i] = wrap_add(req[i], B[i + 1]);                     // :253-255
+        const int64_t r = ordreq[i] < P.c[i] ? ordreq[i] : P.c[i];  // :263
+        // :260-265 np.minimum(., [I[t,1:], inf]) in float64, then astype(int64):
+        // the last stage's cap is +inf but the f64 round trip still rounds |r| > 2^53
+        R[i] = (i + 1 < M1) ? min_via_f64(r, I[i + 1]) : (int64_t)(double)r;
+    }
+#pragma unroll
+    for (int i = 0; i < M1; i++) Icur[i] = wrap_add(I[i], l0(i) ? R[i] : arrival(i));   // :271-277
+#pragma unroll
+    for (int i = 1; i < M1; i++) Icur[i] = wrap_sub(Icur[i], R[i]); // :300 (reference quirk, kept)
+#pragma unroll
+    for (int i = 0; i < M1; i++) {
+        Sv[i + 1] = R[i];                                           // :295
+        U[i + 1] = wrap_sub(ordreq[i], R[i]);                       // :304
+    }
+}
+
+// Sales (:284-303): the demand d and the retailer's backlog against its stock
+__device__ __forceinline__ void im_sales(int64_t d, int64_t B0, int64_t &Icur0, int64_t &Sv0, int64_t &U0) {
+    const int64_t dfill = wrap_add(d, B0);                          // :284-286
+    const int64_t s0 = Icur0 < dfill ? Icur0 : dfill;               // :288
+    Icur0 = wrap_sub(Icur0, s0);
+    Sv0 = s0;
+    U0 = wrap_sub(dfill, s0);                                       // :303
+}
+
+// Profit (:315-321), undiscounted: the caller multiplies by alpha ** t (:322)
+template <int M1>
+__device__ __forceinline__ double im_profit(const ImParams &P, const int64_t (&Sv)[M1 + 1], const int64_t (&U)[M1 + 1],
+                                            const int64_t (&Icur)[M1]) {
+    double term[M1 + 1];
+#pragma unroll
+    for (int q = 0; q <= M1; q++) {
+        const double Sj = (double)Sv[q];
+        const int64_t inv = (q < M1) ? Icur[q] : 0;
+        const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
+        term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
+    }
+    return np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
+}
+
+// Step info (:334-345) into the env's record rr: S[t], U[t], then the f64 bits
+// of the period_profit, revenue, procurement, holding and penalty sums
+template <int M1>
+__device__ __forceinline__ void im_info_record(const ImParams &P, int64_t *rr, const int64_t (&Sv)[M1 + 1],
+                                               const int64_t (&U)[M1 + 1], const int64_t (&Icur)[M1], double profit) {
+#pragma unroll
+    for (int q = 0; q <= M1; q++) {
+        rr[q] = Sv[q];
+        rr[M1 + 1 + q] = U[q];
+    }
+    const double rev = np_sum<double>(M1 + 1, [&](int q) { return P.up[q] * (double)Sv[q]; });
+    const double pro = np_sum<double>(M1 + 1, [&](int q) { return P.uc[q] * (double)Sv[q]; });
+    const double hol = np_sum<double>(M1 + 1, [&](int q) {
+        const int64_t inv = (q < M1) ? Icur[q] : 0;
+        return P.hc[q] * (double)(inv > 0 ? inv : 0);
+    });
+    const double pen = np_sum<double>(M1 + 1, [&](int q) { return P.kc[q] * (double)U[q]; });
+    rr[2 * (M1 + 1) + 0] = __double_as_longlong(profit);
+    rr[2 * (M1 + 1) + 1] = __double_as_longlong(rev);
+    rr[2 * (M1 + 1) + 2] = __double_as_longlong(pro);
+    rr[2 * (M1 + 1) + 3] = __double_as_longlong(hol);
+    rr[2 * (M1 + 1) + 4] = __double_as_longlong(pen);
+}
+
+// evaluate_agent's per-step sums (benchmark_InvManagementBacklogEnv.py:378-399);
+// the caller adds the reward (met[0]) and the step count (met[1])
+template <int M1>
+__device__ __forceinline__ void im_metric_sums(double *met, int64_t d, int64_t Sv0, int64_t U0,
+                                               const int64_t (&Icur)[M1]) {
+    met[2] += (double)d;                                            // demand_realized
+    met[3] += (double)Sv0;                                          // sales[0]
+    met[4] += (double)U0;                                           // unfulfilled[0]
+    int64_t es = 0;                                                 // sum(max(0, ending_inventory))
+#pragma unroll
+    for (int i = 0; i < M1; i++) es = wrap_add(es, Icur[i] > 0 ? Icur[i] : 0);
+    met[5] += (double)es;
+}
+
+// BaseStockAgent.get_action (benchmark_InvManagementBacklogEnv.py:152-198) for
+// one stage: order up to (L + 1) * mu * sf over the inventory position pos (on
+// hand + the requested orders of the last L periods, summed by the caller), in
+// float64, clipped to [0, c], truncated to int64
+__device__ __forceinline__ int64_t im_base_stock_order(const PolicyIO &pol, int L, int64_t pos, int64_t c) {
+    const double target = ((double)(L + 1) * pol.mu) * pol.sf;      // (lead_times + 1) * mu * sf
+    double x = target - (double)pos;
+    x = (x > 0) ? x : 0.0;                                          // np.maximum(0, .)
+    x = (x < 0.0) ? 0.0 : x;                                        // np.clip(., low = 0, high = c)
+    x = (x > (double)c) ? (double)c : x;
+    return (int64_t)x;                                              // astype(int64)
+}
+
+// The PTRS right-hand-side table (or, without one, any valid words) into a
+// TableStage bound for dst in LDS: a fixed count of clamped loads, issued in
+// front of the caller's other loads and flushed to LDS once those are in flight
+__device__ __forceinline__ TableStage im_stage_table(const ImParams &P, double *dst, int lane, bool has_tab) {
+    TableStage ts;
+    ts.dst = dst;
+    const double *tsrc = has_tab ? P.rhs : P.alpha_pow;             // any valid pointer
+    const int qm = has_tab ? P.pc.nk - 1 : 0;
+#pragma unroll
+    for (int u = 0; u < TableStage::NT; u++) ts.v[u] = tsrc[min(lane + u * WAVE, qm)];
+    return ts;
+}
+
 // The step's state stores (ring rows, action_log row, I, B; ImPending holds the
 // first two).  vmcnt counts stores as well as loads on gfx9, so a wait for a
 // load issued after a store also waits for that store; the multi-step kernels
@@ -149,7 +274,7 @@ __device__ __forceinline__ bool im_step_regs(const ImParams &P, int64_t e, bool 
     const bool leader = valid && j == 0;   // state writes
     // Phase A: every load of the step up front (actions, arrivals, this lane's
     // share of the observation window) so the latency overlaps the demand draw
-    int64_t req[M1], ordreq[M1], R[M1], arr[M1];
+    int64_t req[M1], R[M1], arr[M1];
 #pragma unroll
     for (int i = 0; i < M1; i++) req[i] = arow[i];
 #pragma unroll
@@ -208,45 +333,13 @@ __device__ __forceinline__ bool im_step_regs(const ImParams &P, int64_t e, bool 
     if (d < 0) d = 0;
     TPROBE(2);
     // Phase C: dynamics (identical in the 4 lanes)
+    int64_t Icur[M1], Sv[M1 + 1], U[M1 + 1];
+    im_orders<M1>(P, req, s.I, s.B, [&](int i) { return arr[i]; }, [&](int i) { return P.L[i] == 0; }, R, Icur, Sv, U);
 #pragma unroll
-    for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;  // :250
-#pragma unroll
-    for (int i = 0; i < M1; i++) {
-        ordreq[i] = wrap_add(req[i], s.B[i + 1]);                   // :253-255
-        const int64_t r = ordreq[i] < P.c[i] ? ordreq[i] : P.c[i];  // :263
-        // :260-265 np.minimum(., [I[t,1:], inf]) in float64, then astype(int64):
-        // the last stage's cap is +inf but the f64 round trip still rounds |r| > 2^53
-        R[i] = (i + 1 < M1) ? min_via_f64(r, s.I[i + 1]) : (int64_t)(double)r;
-    }
-    int64_t Icur[M1];
-#pragma unroll
-    for (int i = 0; i < M1; i++) {
-        const int L = P.L[i];
-        Icur[i] = wrap_add(s.I[i], L == 0 ? R[i] : arr[i]);
-        pend.R[i] = R[i];                                           // ring slot t mod L <- R[t] (:267)
-    }
+    for (int i = 0; i < M1; i++) pend.R[i] = R[i];                  // ring slot t mod L <- R[t] (:267)
     pend.t = t;
-    const int64_t dfill = wrap_add(d, s.B[0]);                      // :284-286
-    const int64_t s0 = Icur[0] < dfill ? Icur[0] : dfill;           // :288
-    Icur[0] = wrap_sub(Icur[0], s0);
-    int64_t Sv[M1 + 1], U[M1 + 1];
-    Sv[0] = s0;
-#pragma unroll
-    for (int i = 0; i < M1; i++) Sv[i + 1] = R[i];                  // :295
-#pragma unroll
-    for (int i = 1; i < M1; i++) Icur[i] = wrap_sub(Icur[i], R[i]); // :300 (reference quirk, kept)
-    U[0] = wrap_sub(dfill, s0);                                     // :303
-#pragma unroll
-    for (int i = 0; i < M1; i++) U[i + 1] = wrap_sub(ordreq[i], R[i]); // :304
-    double term[M1 + 1];                                            // :315-321
-#pragma unroll
-    for (int q = 0; q <= M1; q++) {
-        const double Sj = (double)Sv[q];
-        const int64_t inv = (q < M1) ? Icur[q] : 0;
-        const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
-        term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
-    }
-    const double profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
+    im_sales(d, s.B[0], Icur[0], Sv[0], U[0]);
+    const double profit = im_profit<M1>(P, Sv, U, Icur);
     reward = apow * profit;                                         // :322
     TPROBE(6);
 #pragma unroll
@@ -254,37 +347,8 @@ __device__ __forceinline__ bool im_step_regs(const ImParams &P, int64_t e, bool 
 #pragma unroll
     for (int q = 0; q <= M1; q++) s.B[q] = BACKLOG ? U[q] : 0;      // :307-312
     dem_out = d;
-    if (irec) {  // step info (inventory_management.py:334-345): S[t], U[t], then the
-                 // f64 bits of period_profit, revenue, procurement, holding, penalty sums
-        constexpr int W = 2 * (M1 + 1) + 5;
-        int64_t *rr = irec + e * W;
-#pragma unroll
-        for (int q = 0; q <= M1; q++) {
-            rr[q] = Sv[q];
-            rr[M1 + 1 + q] = U[q];
-        }
-        const double rev = np_sum<double>(M1 + 1, [&](int q) { return P.up[q] * (double)Sv[q]; });
-        const double pro = np_sum<double>(M1 + 1, [&](int q) { return P.uc[q] * (double)Sv[q]; });
-        const double hol = np_sum<double>(M1 + 1, [&](int q) {
-            const int64_t inv = (q < M1) ? Icur[q] : 0;
-            return P.hc[q] * (double)(inv > 0 ? inv : 0);
-        });
-        const double pen = np_sum<double>(M1 + 1, [&](int q) { return P.kc[q] * (double)U[q]; });
-        rr[2 * (M1 + 1) + 0] = __double_as_longlong(profit);
-        rr[2 * (M1 + 1) + 1] = __double_as_longlong(rev);
-        rr[2 * (M1 + 1) + 2] = __double_as_longlong(pro);
-        rr[2 * (M1 + 1) + 3] = __double_as_longlong(hol);
-        rr[2 * (M1 + 1) + 4] = __double_as_longlong(pen);
-    }
-    if (met) {   // evaluate_agent metrics (benchmark_InvManagementBacklogEnv.py:378-399)
-        met[2] += (double)d;                                        // demand_realized
-        met[3] += (double)Sv[0];                                    // sales[0]
-        met[4] += (double)U[0];                                     // unfulfilled[0]
-        int64_t es = 0;                                             // sum(max(0, ending_inventory))
-#pragma unroll
-        for (int i = 0; i < M1; i++) es = wrap_add(es, Icur[i] > 0 ? Icur[i] : 0);
-        met[5] += (double)es;
-    }
+    if (irec) im_info_record<M1>(P, irec + e * (2 * (M1 + 1) + 5), Sv, U, Icur, profit);
+    if (met) im_metric_sums<M1>(met, d, Sv[0], U[0], Icur);
     if (orow) {                                                     // :354-391
         int64_t *w = orow + M1;
         if (j == 0) {
@@ -376,10 +440,9 @@ __device__ __forceinline__ void im_flush_pending(const ImParams &P, const ImPend
     }
 }
 
-// BaseStockAgent.get_action (benchmark_InvManagementBacklogEnv.py:152-198): order
-// up to (L_i + 1) * mu * sf over the inventory position on hand + requested
-// orders of the last L_i periods (action_log[max(0, t - L_i) : t, i]), in
-// float64, clipped to [0, c_i], truncated to int64.
+// BaseStockAgent.get_action with the inventory position summed from the
+// action_log ring: on hand + the requested orders of the last L_i periods
+// (action_log[max(0, t - L_i) : t, i])
 template <int M1, bool BACKLOG, class G = Pcg>
 __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO &pol, const ImState<M1, BACKLOG, G> &st,
                                               int t, int64_t e, int64_t (&act)[M1]) {
@@ -398,12 +461,7 @@ __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO 
             }
             pos = wrap_add(pos, pipe);
         }
-        const double target = ((double)(L + 1) * pol.mu) * pol.sf;   // (lead_times + 1) * mu * sf
-        double x = target - (double)pos;
-        x = (x > 0) ? x : 0.0;                                      // np.maximum(0, .)
-        x = (x < 0.0) ? 0.0 : x;                                    // np.clip(., low = 0, high = c)
-        x = (x > (double)P.c[i]) ? (double)P.c[i] : x;
-        act[i] = (int64_t)x;                                        // astype(int64)
+        act[i] = im_base_stock_order(pol, L, pos, P.c[i]);
     }
 }
 
@@ -558,15 +616,7 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     const double apow0 = P.alpha_pow[tc];
     const int64_t udem0 = P.user_D[tc];
     double *rhs_l = reinterpret_cast<double *>(im_tile + (int64_t)EPW * O);
-    TableStage ts;
-    ts.dst = rhs_l;
-    {
-        const bool has_tab = P.pc.nk > 0;
-        const double *tsrc = has_tab ? P.rhs : P.alpha_pow;   // any valid pointer
-        const int qm = has_tab ? P.pc.nk - 1 : 0;
-#pragma unroll
-        for (int u = 0; u < TableStage::NT; u++) ts.v[u] = tsrc[min(lane + u * WAVE, qm)];
-    }
+    TableStage ts = im_stage_table(P, rhs_l, lane, P.pc.nk > 0);
 
     // state rows are Npad wide, so every lane loads unconditionally (straight-line
     // loads keep the compiler's vmcnt waits exact); lanes past N take the last
@@ -657,8 +707,7 @@ __device__ __forceinline__ void wg_lds_sync() {
 //                     the dynamics, then (after the handoff of d through LDS)
 //                     sales, backlog, reward, the tile's inventory and newest
 //                     action row, and the state / output stores
-// Both waves then store half of the observation tile.  Same arithmetic, in
-// the same order, as im_step_regs (inventory_management.py:224-352).
+// Both waves then store half of the observation tile.
 // With the lookahead (AHEAD) the dynamics wave loads d from the cache itself,
 // so it computes as soon as its own loads land, and the waves meet only once,
 // when the tile is complete (the window wave leaves the newest row's words to
@@ -752,16 +801,7 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
     double *rhs_l = reinterpret_cast<double *>(im_tile + (int64_t)WAVE * M1 * (D + 1));
     // the other lookahead slot (a P field and an argument behind P: formed where it is stored to)
     auto anxt = [&]() -> uint64_t * { return P.ahead ? P.ahead + (int64_t)(cur ^ 1) * 4 * S : nullptr; };
-    auto stage_table = [&](int lane) {
-        TableStage ts;
-        ts.dst = rhs_l;
-        const bool has_tab = P.pc.nk > 0 && P.dist == 1;
-        const double *tsrc = has_tab ? P.rhs : P.alpha_pow;    // any valid pointer
-        const int qm = has_tab ? P.pc.nk - 1 : 0;
-#pragma unroll
-        for (int u = 0; u < TableStage::NT; u++) ts.v[u] = tsrc[min(lane + u * WAVE, qm)];
-        return ts;
-    };
+    auto stage_table = [&](int lane) { return im_stage_table(P, rhs_l, lane, P.pc.nk > 0 && P.dist == 1); };
     auto draw = [&](auto &g, uint64_t &u32) -> int64_t {
 #ifdef INVSIM_ABL_NO_POISSON  // profiling ablation build only (wrong results)
         int64_t x = 20 + (int64_t)(g.lo & 3);
@@ -1033,69 +1073,21 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
         wslot = wslot >= D ? wslot - D : wslot;
         alogw = P.alog;
     }
-    int64_t ordreq[M1], R[M1], Icur[M1];
-#pragma unroll
-    for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;  // :250
-#pragma unroll
-    for (int i = 0; i < M1; i++) {
-        ordreq[i] = wrap_add(req[i], B[i + 1]);                     // :253-255
-        const int64_t r = ordreq[i] < P.c[i] ? ordreq[i] : P.c[i];  // :263
-        R[i] = (i + 1 < M1) ? min_via_f64(r, I[i + 1]) : (int64_t)(double)r;   // :260-265
-    }
-#pragma unroll
-    for (int i = 0; i < M1; i++) Icur[i] = wrap_add(I[i], P.L[i] == 0 ? R[i] : arr[i]);
-#pragma unroll
-    for (int i = 1; i < M1; i++) Icur[i] = wrap_sub(Icur[i], R[i]); // :300 (reference quirk, kept)
-    int64_t Sv[M1 + 1], U[M1 + 1];
-#pragma unroll
-    for (int i = 0; i < M1; i++) {
-        Sv[i + 1] = R[i];                                           // :295
-        U[i + 1] = wrap_sub(ordreq[i], R[i]);                       // :304
-    }
+    int64_t R[M1], Icur[M1], Sv[M1 + 1], U[M1 + 1];
+    im_orders<M1>(P, req, I, B, [&](int i) { return arr[i]; }, [&](int i) { return P.L[i] == 0; }, R, Icur, Sv, U);
     if (!DEC) wg_lds_sync();   // d from the demand wave
     if (DEC) TWAIT();     // (TIMING build: probe 1 after the loads land)
     TPROBE_AT(1, WAVE);   // the dynamics wave: loads in, d handed over
     const int64_t d = DEC ? d_ahead : dsh[lane];
-    const int64_t dfill = wrap_add(d, B[0]);                        // :284-286
-    const int64_t s0 = Icur[0] < dfill ? Icur[0] : dfill;           // :288
-    Icur[0] = wrap_sub(Icur[0], s0);
-    Sv[0] = s0;
-    U[0] = wrap_sub(dfill, s0);                                     // :303
+    im_sales(d, B[0], Icur[0], Sv[0], U[0]);
     // the reward (:315-322); nothing in the obs tile needs it
     double profit = 0.0, reward = 0.0;
     auto reward_chain = [&]() {
-        double term[M1 + 1];
-#pragma unroll
-        for (int q = 0; q <= M1; q++) {
-            const double Sj = (double)Sv[q];
-            const int64_t inv = (q < M1) ? Icur[q] : 0;
-            const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
-            term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
-        }
-        profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
+        profit = im_profit<M1>(P, Sv, U, Icur);
         reward = apow * profit;                                     // :322
     };
-    auto info_record = [&]() {   // step info (:334-345), as im_step_regs
-        if (!P.cm.info_rec) return;
-        constexpr int W = 2 * (M1 + 1) + 5;
-        int64_t *rr = (int64_t *)P.cm.info_rec + e * W;
-#pragma unroll
-        for (int q = 0; q <= M1; q++) {
-            rr[q] = Sv[q];
-            rr[M1 + 1 + q] = U[q];
-        }
-        const double rev = np_sum<double>(M1 + 1, [&](int q) { return P.up[q] * (double)Sv[q]; });
-        const double pro = np_sum<double>(M1 + 1, [&](int q) { return P.uc[q] * (double)Sv[q]; });
-        const double hol = np_sum<double>(M1 + 1, [&](int q) {
-            const int64_t inv = (q < M1) ? Icur[q] : 0;
-            return P.hc[q] * (double)(inv > 0 ? inv : 0);
-        });
-        const double pen = np_sum<double>(M1 + 1, [&](int q) { return P.kc[q] * (double)U[q]; });
-        rr[2 * (M1 + 1) + 0] = __double_as_longlong(profit);
-        rr[2 * (M1 + 1) + 1] = __double_as_longlong(rev);
-        rr[2 * (M1 + 1) + 2] = __double_as_longlong(pro);
-        rr[2 * (M1 + 1) + 3] = __double_as_longlong(hol);
-        rr[2 * (M1 + 1) + 4] = __double_as_longlong(pen);
+    auto info_record = [&]() {
+        if (P.cm.info_rec) im_info_record<M1>(P, (int64_t *)P.cm.info_rec + e * (2 * (M1 + 1) + 5), Sv, U, Icur, profit);
     };
     auto tile_half = [&]() {
         const int64_t h = thalf < tcount ? thalf : tcount;
@@ -1234,7 +1226,6 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
 // Chunk handoff (c = 0, 1, ...): the demand wave fills buffer c & 1, then
 // barrier c; the dynamics wave consumes chunk c after barrier c, so the
 // demand wave's refill of a buffer follows the dynamics wave's use of it.
-// Same arithmetic, in the same order, as im_step_regs.
 // The demand wave of the rollout kernels (stream_flat_loop): Poisson demand
 // (:280) of each launch step into the ring dbuf [RD * CH][WAVE], nb barriers
 template <int CH, int RD, class RG>
@@ -1310,15 +1301,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
     const int K = io.K;
     const int nch = (K + CH - 1) / CH;
     if (threadIdx.x < WAVE) {   // ---- demand wave
-        TableStage ts;
-        ts.dst = rhs_l;
-        {
-            const bool has_tab = P.pc.nk > 0;
-            const double *tsrc = has_tab ? P.rhs : P.alpha_pow;   // any valid pointer
-            const int qm = has_tab ? P.pc.nk - 1 : 0;
-#pragma unroll
-            for (int u = 0; u < TableStage::NT; u++) ts.v[u] = tsrc[min(lane + u * WAVE, qm)];
-        }
+        TableStage ts = im_stage_table(P, rhs_l, lane, P.pc.nk > 0);
         RG g;
         P.cm.rng.load(el, g);
         ts.flush(lane);
@@ -1428,12 +1411,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                                 if (t - a >= 0) pipe = wrap_add(pipe, v);
                             }
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
-                            const double target = ((double)(G::lt(i) + 1) * pol.mu) * pol.sf;
-                            double x = target - (double)pos;
-                            x = (x > 0) ? x : 0.0;                              // np.maximum(0, .)
-                            x = (x < 0.0) ? 0.0 : x;                            // np.clip(., 0, c)
-                            x = (x > (double)P.c[i]) ? (double)P.c[i] : x;
-                            req[i] = (int64_t)x;
+                            req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
                         }
                     } else {
 #pragma unroll
@@ -1444,52 +1422,14 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                         for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
                     }
                 }
-                int64_t ordreq[M1], R[M1], Icur[M1];
-#pragma unroll
-                for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;   // :250
-#pragma unroll
-                for (int i = 0; i < M1; i++) {
-                    ordreq[i] = wrap_add(req[i], B[i + 1]);                     // :253-255
-                    const int64_t r = ordreq[i] < P.c[i] ? ordreq[i] : P.c[i];  // :263
-                    R[i] = (i + 1 < M1) ? min_via_f64(r, I[i + 1]) : (int64_t)(double)r;   // :260-265
-                }
-#pragma unroll
-                for (int i = 0; i < M1; i++) {                                  // arrivals (:271-277)
-                    const int L = G::lt(i);
-                    const int64_t arr = (L > 0 && t >= L) ? rw[i][0] : 0;
-                    Icur[i] = wrap_add(I[i], L == 0 ? R[i] : arr);
-                }
-#pragma unroll
-                for (int i = 1; i < M1; i++) Icur[i] = wrap_sub(Icur[i], R[i]); // :300 (reference quirk, kept)
-                int64_t Sv[M1 + 1], U[M1 + 1];
-#pragma unroll
-                for (int i = 0; i < M1; i++) {
-                    Sv[i + 1] = R[i];                                           // :295
-                    U[i + 1] = wrap_sub(ordreq[i], R[i]);                       // :304
-                }
-                const int64_t dfill = wrap_add(d, B[0]);                        // :284-286
-                const int64_t s0 = Icur[0] < dfill ? Icur[0] : dfill;           // :288
-                Icur[0] = wrap_sub(Icur[0], s0);
-                Sv[0] = s0;
-                U[0] = wrap_sub(dfill, s0);                                     // :303
-                double term[M1 + 1];                                            // :315-321
-#pragma unroll
-                for (int q = 0; q <= M1; q++) {
-                    const double Sj = (double)Sv[q];
-                    const int64_t inv = (q < M1) ? Icur[q] : 0;
-                    const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
-                    term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
-                }
-                const double profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
-                const double reward = apow * profit;                            // :322
-                if (POL) {   // evaluate_agent metrics (benchmark_InvManagementBacklogEnv.py:378-399)
-                    met[2] += (double)d;                                        // demand_realized
-                    met[3] += (double)Sv[0];                                    // sales[0]
-                    met[4] += (double)U[0];                                     // unfulfilled[0]
-                    int64_t es = 0;                                             // sum(max(0, ending_inventory))
-#pragma unroll
-                    for (int i = 0; i < M1; i++) es = wrap_add(es, Icur[i] > 0 ? Icur[i] : 0);
-                    met[5] += (double)es;
+                int64_t R[M1], Icur[M1], Sv[M1 + 1], U[M1 + 1];
+                im_orders<M1>(
+                    P, req, I, B, [&](int i) { return (G::lt(i) > 0 && t >= G::lt(i)) ? rw[i][0] : (int64_t)0; },
+                    [](int i) { return G::lt(i) == 0; }, R, Icur, Sv, U);
+                im_sales(d, B[0], Icur[0], Sv[0], U[0]);
+                const double reward = apow * im_profit<M1>(P, Sv, U, Icur);     // :322
+                if (POL) {
+                    im_metric_sums<M1>(met, d, Sv[0], U[0], Icur);
                     met[0] += reward;                                           // episode_reward += reward
                     met[1] += 1.0;                                              // episode_steps
                 }
@@ -1616,8 +1556,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
 // the previous step's stores (vmcnt is in order).  One barrier per chunk: the
 // demand wave fills dbuf[c & 1] before barrier c, the dynamics wave consumes it
 // between barriers c and c + 1 and fills ibuf[c & 1], which the obs wave
-// consumes between barriers c + 1 and c + 2.  Same arithmetic, in the same
-// order, as im_step_regs.
+// consumes between barriers c + 1 and c + 2.
 #ifndef IM_ROLL3O_CH
 #define IM_ROLL3O_CH 2   // swept on MI355X (LostSales 32768 envs): (CH, RD) = (2, 8) 65.6 us, (4, 4) 67.0, (4, 8) 66.5, (8, 4) 74.6
 #endif
@@ -1679,15 +1618,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     TPROBE_W(0);
     TPROBE_W_ID();
     if (role == 0) {   // ---- demand wave
-        TableStage ts;
-        ts.dst = rhs_l;
-        {
-            const bool has_tab = P.pc.nk > 0;
-            const double *tsrc = has_tab ? P.rhs : P.alpha_pow;   // any valid pointer
-            const int qm = has_tab ? P.pc.nk - 1 : 0;
-#pragma unroll
-            for (int u = 0; u < TableStage::NT; u++) ts.v[u] = tsrc[min(lane + u * WAVE, qm)];
-        }
+        TableStage ts = im_stage_table(P, rhs_l, lane, P.pc.nk > 0);
         RG g;
         P.cm.rng.load(el, g);
         for (int q = lane; q < P.periods; q += WAVE) ap_l[q] = P.alpha_pow[q];   // before barrier 0
@@ -1871,12 +1802,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                             for (int a = 0; a < G::lt(i); a++)                  // action_log[max(0, t - L_i) : t, i]
                                 if (t - 1 - a >= 0) pipe = wrap_add(pipe, hv[i][a]);
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
-                            const double target = ((double)(G::lt(i) + 1) * pol.mu) * pol.sf;
-                            double x = target - (double)pos;
-                            x = (x > 0) ? x : 0.0;                              // np.maximum(0, .)
-                            x = (x < 0.0) ? 0.0 : x;                            // np.clip(., 0, c)
-                            x = (x > (double)P.c[i]) ? (double)P.c[i] : x;
-                            req[i] = (int64_t)x;
+                            req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
                         }
                     } else {
 #pragma unroll
@@ -1887,52 +1813,14 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                         for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
                     }
                 }
-                int64_t ordreq[M1], R[M1], Icur[M1];
-#pragma unroll
-                for (int i = 0; i < M1; i++) req[i] = req[i] > 0 ? req[i] : 0;   // :250
-#pragma unroll
-                for (int i = 0; i < M1; i++) {
-                    ordreq[i] = wrap_add(req[i], B[i + 1]);                     // :253-255
-                    const int64_t r = ordreq[i] < P.c[i] ? ordreq[i] : P.c[i];  // :263
-                    R[i] = (i + 1 < M1) ? min_via_f64(r, I[i + 1]) : (int64_t)(double)r;   // :260-265
-                }
-#pragma unroll
-                for (int i = 0; i < M1; i++) {                                  // arrivals (:271-277)
-                    const int L = G::lt(i);
-                    const int64_t arr = (L > 0 && t >= L) ? rw[i][0] : 0;
-                    Icur[i] = wrap_add(I[i], L == 0 ? R[i] : arr);
-                }
-#pragma unroll
-                for (int i = 1; i < M1; i++) Icur[i] = wrap_sub(Icur[i], R[i]); // :300 (reference quirk, kept)
-                int64_t Sv[M1 + 1], U[M1 + 1];
-#pragma unroll
-                for (int i = 0; i < M1; i++) {
-                    Sv[i + 1] = R[i];                                           // :295
-                    U[i + 1] = wrap_sub(ordreq[i], R[i]);                       // :304
-                }
-                const int64_t dfill = wrap_add(d, B[0]);                        // :284-286
-                const int64_t s0 = Icur[0] < dfill ? Icur[0] : dfill;           // :288
-                Icur[0] = wrap_sub(Icur[0], s0);
-                Sv[0] = s0;
-                U[0] = wrap_sub(dfill, s0);                                     // :303
-                double term[M1 + 1];                                            // :315-321
-#pragma unroll
-                for (int q = 0; q <= M1; q++) {
-                    const double Sj = (double)Sv[q];
-                    const int64_t inv = (q < M1) ? Icur[q] : 0;
-                    const double hold = P.hc[q] * (double)(inv > 0 ? inv : 0);
-                    term[q] = ((P.up[q] * Sj - P.uc[q] * Sj) - hold) - P.kc[q] * (double)U[q];
-                }
-                const double profit = np_sum<double>(M1 + 1, [&](int q) { return term[q]; });
-                const double reward = apow * profit;                            // :322
-                if (POL) {   // evaluate_agent metrics (benchmark_InvManagementBacklogEnv.py:378-399)
-                    met[2] += (double)d;                                        // demand_realized
-                    met[3] += (double)Sv[0];                                    // sales[0]
-                    met[4] += (double)U[0];                                     // unfulfilled[0]
-                    int64_t es = 0;                                             // sum(max(0, ending_inventory))
-#pragma unroll
-                    for (int i = 0; i < M1; i++) es = wrap_add(es, Icur[i] > 0 ? Icur[i] : 0);
-                    met[5] += (double)es;
+                int64_t R[M1], Icur[M1], Sv[M1 + 1], U[M1 + 1];
+                im_orders<M1>(
+                    P, req, I, B, [&](int i) { return (G::lt(i) > 0 && t >= G::lt(i)) ? rw[i][0] : (int64_t)0; },
+                    [](int i) { return G::lt(i) == 0; }, R, Icur, Sv, U);
+                im_sales(d, B[0], Icur[0], Sv[0], U[0]);
+                const double reward = apow * im_profit<M1>(P, Sv, U, Icur);     // :322
+                if (POL) {
+                    im_metric_sums<M1>(met, d, Sv[0], U[0], Icur);
                     met[0] += reward;                                           // episode_reward += reward
                     met[1] += 1.0;                                              // episode_steps
 #pragma unroll
@@ -2129,8 +2017,6 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
 // the arguments of a launch, in the kernel's order (q: its ImParams, ha: the above)
 #define IM_SPLIT_ARGS io.act, q.I, q.B, q.Rring, q.alog32, ha.acur, ha.n32, ha.hw, q, t_u, io, cur, ha.apow, ha.n, ha.nw, ha.trunc
 
-}  // namespace
-
 #define IM_DISPATCH(M1V, BL, LAUNCH)                                  \
     switch (M1V) {                                                     \
         case 1: if (BL) LAUNCH(1, true); else LAUNCH(1, false); break; \
@@ -2144,11 +2030,16 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
         default: return hipErrorInvalidValue;                          \
     }
 
-#ifdef INVSIM_IM_FAST_TU
-// invmgmt_ph.hip: this file compiled a second time for the fast-stream run
-// kernels (a TU of their own, so the two instantiation sets compile in parallel)
-hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                            const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
+// The split / rollout / run dispatch of one demand stream: RG = Pcg (numpy's
+// PCG64, parity) or PhiloxGen (the fast stream; instantiated in
+// invmgmt_ph.hip).  The parity stream's lookahead cache holds generator state,
+// which is committed to cm.rng (im_commit_launch) before a kernel that reads
+// cm.rng; the fast stream's holds demands only: it is never committed, and any
+// other launch leaves it stale (the launch-step counter moves past it).
+template <class RG>
+hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
+                        const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
+    constexpr bool ph = RG::kCounter;
     sunk = im_sink_noop(p, t_u, pol, io);
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
     const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
@@ -2156,13 +2047,21 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
     PolicyIO none{};
     const PolicyIO &pv = pol ? *pol : none;
     const bool npd = p.dist >= 2 && p.dist <= 4;
-    if (im_split_applies(p, t_u, pol, io)) {   // the split step kernel, with the demand-only lookahead
+    if (im_split_applies(p, t_u, pol, io)) {
         const size_t lds2 = lds + WAVE * sizeof(int64_t);
+        const dim3 block2(2 * WAVE);
         ImParams q = p;
         if (!p.cm.kn.im_ahead) q.ahead = nullptr;
+        if constexpr (!ph) {
+            if (ahead && !q.ahead) {      // lookahead switched off: commit, then draw inline
+                const hipError_t ce = im_commit_launch(p, slot, s);
+                ahead = false;
+                if (ce != hipSuccess) return ce;
+            }
+        }
         const bool hit = ahead && q.ahead;
-        const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;
-        const dim3 grid2(grid.x + gla), block2(2 * WAVE);
+        const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;   // lookahead workgroups
+        const dim3 grid2(grid.x + gla);
         const int cur = slot;
         // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
         if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
@@ -2171,34 +2070,45 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
 #define S_(M, B)                                                                                        \
     do {                                                                                                \
         if (npd) {                                                                                      \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, RG, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
         } else {                                                                                        \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, PhiloxGen>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
+            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, RG, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
+            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
         }                                                                                               \
     } while (0)
         IM_DISPATCH(M1, backlog, S_)
 #undef S_
         sunk = true;                  // the split kernel folds into the episode sink (if one is set)
-        ahead = q.ahead != nullptr;   // every env drew launch step ph_step + 1 into slot cur ^ 1
+        ahead = q.ahead != nullptr;   // every env drew its next demand into slot cur ^ 1
         if (ahead) slot ^= 1;
         return hipGetLastError();
     }
-    // any other launch moves the counter past the cached step: the cache is stale
-    ahead = false;
+    if constexpr (ph) {
+        ahead = false;
+    } else if (!(!pol && io.K == 1 && t_u >= p.periods) && ahead) {
+        // the one-wave kernel draws from the committed state (brought into
+        // cm.rng first): the cache is stale after it, unless this launch is the
+        // lock-step autoreset (no draw)
+        const hipError_t ce = im_commit_launch(p, slot, s);
+        ahead = false;
+        if (ce != hipSuccess) return ce;
+    }
+    // lock-step rollout of the reference's default lead times: register windows
+    // and a demand wave (im_roll3_kernel / im_roll3o_kernel), open loop or with
+    // the in-kernel BaseStock / ConstantOrder agents
     if (im_roll_applies(p, M1, t_u, pol, io)) {
         sunk = true;                  // so do the rollout kernels
-        return im_roll_launch<PhiloxGen>(p, backlog, t_u, pol, io, s);
+        return im_roll_launch<RG>(p, backlog, t_u, pol, io, s);
     }
 #define K_(M, B, TU, ONE, POL)                                                                          \
     do {                                                                                                \
         if (npd)                                                                                        \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, true, PhiloxGen>), grid, block, lds, s, p, t_u, io, pv);  \
+            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, true, RG>), grid, block, lds, s, p, t_u, io, pv);  \
         else                                                                                            \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, false, PhiloxGen>), grid, block, lds, s, p, t_u, io, pv); \
+            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, false, RG>), grid, block, lds, s, p, t_u, io, pv); \
     } while (0)
 #define L_(M, B)                                             \
     do {                                                     \
@@ -2219,99 +2129,22 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
     return hipGetLastError();
 }
 
+}  // namespace
+
+#ifdef INVSIM_IM_FAST_TU
+// invmgmt_ph.hip: this file compiled a second time for the fast-stream
+// kernels (a TU of their own, so the two instantiation sets compile in parallel)
+hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
+                            const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
+    return im_launch_rg<PhiloxGen>(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);
+}
+
 INVSIM_PTRS_STATS_TU(im_ph)
 #else
 hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                          const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
-    sunk = im_sink_noop(p, t_u, pol, io);
-    if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
-    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
-    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
-    const bool npd = p.dist >= 2 && p.dist <= 4;
-    const bool ph = p.cm.philox != 0;       // fast stream: invmgmt_ph.hip (split / rollout / run kernels, no lookahead)
-    if (ph) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);   // (a cache is the fast stream's)
-    if (im_split_applies(p, t_u, pol, io)) {
-        const size_t lds2 = lds + WAVE * sizeof(int64_t);
-        const dim3 block2(2 * WAVE);
-        ImParams q = p;
-        if (!p.cm.kn.im_ahead) q.ahead = nullptr;
-        if (ahead && !q.ahead) {      // lookahead switched off: commit, then draw inline
-            const hipError_t ce = im_commit_launch(p, slot, s);
-            ahead = false;
-            if (ce != hipSuccess) return ce;
-        }
-        const bool hit = ahead && q.ahead;
-        const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;   // lookahead workgroups
-        const dim3 grid2(grid.x + gla);
-        const int cur = slot;
-        // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
-        if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
-        const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
-        const bool early = p.cm.N > IM_EARLY_STORES_MIN_N;   // the EARLY instantiation (lookahead steps only)
-#define S_(M, B)                                                                                        \
-    do {                                                                                                \
-        if (npd) {                                                                                      \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, Pcg, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
-        } else {                                                                                        \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, Pcg, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
-        }                                                                                               \
-    } while (0)
-        IM_DISPATCH(M1, backlog, S_)
-#undef S_
-        sunk = true;                  // the split kernel folds into the episode sink (if one is set)
-        if (q.ahead) {                // every env drew its next demand into slot cur ^ 1
-            ahead = true;
-            slot ^= 1;
-        } else {
-            ahead = false;
-        }
-        return hipGetLastError();
-    }
-    // the one-wave kernel draws from the committed state (brought into cm.rng
-    // first): the cache is stale after it, unless this launch is the lock-step
-    // autoreset (no draw)
-    if (!(!pol && io.K == 1 && t_u >= p.periods) && ahead) {
-        const hipError_t ce = im_commit_launch(p, slot, s);
-        ahead = false;
-        if (ce != hipSuccess) return ce;
-    }
-    // lock-step rollout of the reference's default lead times: register windows
-    // and a demand wave (im_roll3_kernel / im_roll3o_kernel), open loop or with
-    // the in-kernel BaseStock / ConstantOrder agents
-    if (im_roll_applies(p, M1, t_u, pol, io)) {
-        sunk = true;                  // so do the rollout kernels
-        return im_roll_launch<Pcg>(p, backlog, t_u, pol, io, s);
-    }
-#define K_(M, B, TU, ONE, POL)                                                                         \
-    do {                                                                                                \
-        if (npd)                                                                                        \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, true, Pcg>), grid, block, lds, s, p, t_u, io, pv);  \
-        else                                                                                            \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, false, Pcg>), grid, block, lds, s, p, t_u, io, pv); \
-    } while (0)
-#define L_(M, B)                                             \
-    do {                                                     \
-        if (pol) {                                           \
-            if (t_u >= 0) K_(M, B, true, false, true);       \
-            else K_(M, B, false, false, true);               \
-        } else if (io.K == 1) {                              \
-            if (t_u >= 0) K_(M, B, true, true, false);       \
-            else K_(M, B, false, true, false);               \
-        } else {                                             \
-            if (t_u >= 0) K_(M, B, true, false, false);      \
-            else K_(M, B, false, false, false);              \
-        }                                                    \
-    } while (0)
-    IM_DISPATCH(M1, backlog, L_)
-#undef L_
-#undef K_
-    return hipGetLastError();
+    if (p.cm.philox) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);   // invmgmt_ph.hip
+    return im_launch_rg<Pcg>(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);
 }
 
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s) {

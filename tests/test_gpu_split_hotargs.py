@@ -265,6 +265,21 @@ def test_info_record(gpu, oracle, monkeypatch):
         assert np.array_equal(_np(infos[0]["demand"]).reshape(n), inf["demand"]), k
         assert np.array_equal(_np(infos[0]["sales"]), inf["sales"]), k
         assert np.array_equal(_np(infos[0]["unfulfilled"]), inf["unfulfilled"]), k
+        # the five f64 sums of both handles against numpy, recomputed from the
+        # oracle's S, U and ending inventory as the reference forms them
+        # (inventory_management.py:314-321; test_compat does it for one env)
+        e0 = envs[0]
+        S, U = inf["sales"], inf["unfulfilled"]
+        rev = e0.unit_price * S
+        pro = e0.unit_cost * S
+        hol = e0.holding_cost * np.maximum(0, np.append(inf["ending_inventory"], np.zeros((n, 1), np.int64), axis=1))
+        pen = e0.demand_cost * U
+        exp = {"period_profit": (rev - pro - hol - pen).sum(axis=1), "revenue": rev.sum(axis=1),
+               "procurement_cost": pro.sum(axis=1), "holding_cost": hol.sum(axis=1), "penalty_cost": pen.sum(axis=1)}
+        for key, v in exp.items():
+            assert v.dtype == np.float64 and v.shape == (n,)
+            for h, got in enumerate(infos):
+                assert np.array_equal(_np(got[key]).view(np.int64), v.view(np.int64)), (key, k, h)
     assert torch.equal(envs[0].get_state(), envs[1].get_state())
 
 
