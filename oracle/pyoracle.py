@@ -485,8 +485,10 @@ class OracleNet(_Base):
     fam = "net"
 
     def __init__(self, n, graph=None, num_periods=30, backlog=True, alpha=1.0, user_D=None, sample_path=None):
-        if graph is None:
-            graph = default_graph()
+        # network_management.py:77 works on graph.copy(): a copy keeps node and successor
+        # order but rebuilds each predecessor list in graph.edges() order, which is the
+        # order the arrival and purchase-cost sums then run in (:516-523, :586-592)
+        graph = default_graph() if graph is None else graph.copy()
         self.n = n
         self.topo = net_tables(graph, num_periods, user_D, sample_path)
         self._t = {k: np.ascontiguousarray(v) for k, v in self.topo["tables"].items()}

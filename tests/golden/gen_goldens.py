@@ -10,6 +10,9 @@ stand-in in `tests/golden/standin/` and records, per env instance, every
 reset observation and every step's (obs, reward, truncated, info fields).
 Nothing from the reference is copied: the fixtures are inputs + outputs only.
 
+Sub-commands: `edges` (adversarial actions at the numeric edges) and `graphs`
+(NetInvMgmtMasterEnv on the graphs of tests/net_graphs.py, net_graph_*.npz).
+
 Episode protocol recorded for env i (seed = base_seed + i, gymnasium
 SyncVectorEnv convention): reset(seed=seed_i); then for each episode
 `ep_len` steps; between episodes reset() WITHOUT a seed (RNG stream continues),
@@ -314,9 +317,82 @@ def gen_edges():
           actions=acts, obs=obs, reward=rew, truncated=trunc, D=D, reset_obs=reset_obs)
 
 
+def graph_actions(rng, n_env, n_step, A):
+    a = rng.uniform(-5.0, 60.0, size=(n_env, n_step, A))
+    u = rng.random((n_env, n_step, A))
+    a[u < 0.2] = np.round(a[u < 0.2]) + 0.5            # exact .5 ties (round half-even)
+    return a.astype(np.float32)
+
+
+def gen_net_graph(name, builder, num_periods, backlog, alpha, n_env=8, n_ep=1, base_seed=7000, act_seed=17):
+    """NetInvMgmtMasterEnv(graph=...) on a graph of tests/net_graphs.py, driven as
+    gen_net drives the built-in graphs.  The market lambdas draw from the env
+    that is being stepped (`holder`), as the reference's own default graph does."""
+    import network_management as ref
+    sys.path.insert(0, os.path.dirname(HERE))
+    import net_graphs
+    holder = {}
+    sampler = lambda fn: (lambda **p: getattr(holder["env"].np_random, fn)(**p))  # noqa: E731
+    mk = lambda: ref.NetInvMgmtMasterEnv(graph=net_graphs.GRAPHS[builder](sampler, num_periods),  # noqa: E731
+                                         num_periods=num_periods, backlog=backlog, alpha=alpha)
+    env0 = mk()
+    ep_len, O = env0.num_periods, env0.obs_dim
+    A, J, RL = len(env0.reorder_links), len(env0.main_nodes), len(env0.retail_links)
+    S = n_ep * ep_len
+    actions = graph_actions(np.random.default_rng(act_seed), n_env, S, A)
+    obs = np.zeros((n_env, S, O), np.float32)
+    rew = np.zeros((n_env, S), np.float64)
+    trunc = np.zeros((n_env, S), np.bool_)
+    rec = {k: np.zeros((n_env, S, w), np.float64) for k, w in
+           (("X", J), ("U", RL), ("D", RL), ("R", A), ("Y", A), ("P", J), ("S", RL))}
+    reset_obs = np.zeros((n_env, n_ep, O), np.float32)
+    for i in range(n_env):
+        env = holder["env"] = mk()
+        for ep in range(n_ep):
+            o, info = env.reset(seed=base_seed + i) if ep == 0 else env.reset()
+            reset_obs[i, ep] = o
+            for k in range(ep_len):
+                s = ep * ep_len + k
+                o, r, te, tr, info = env.step(actions[i, s])
+                obs[i, s], rew[i, s], trunc[i, s] = o, r, tr
+                assert not te
+                rec["X"][i, s] = env.X.loc[k + 1].values
+                rec["U"][i, s] = env.U.loc[k + 1].values
+                rec["D"][i, s] = env.D.loc[k].values
+                rec["R"][i, s] = env.R.loc[k].values
+                rec["Y"][i, s] = env.Y.loc[k + 1].values
+                rec["P"][i, s] = env.P.loc[k].values
+                rec["S"][i, s] = env.S.loc[k, env.retail_links].values      # market sales S[t]
+    topo = dict(main_nodes=[int(x) for x in env0.main_nodes],
+                reorder_links=[[int(a), int(b)] for a, b in env0.reorder_links],
+                retail_links=[[int(a), int(b)] for a, b in env0.retail_links],
+                obs_dim=int(O), backlog=bool(env0.backlog))
+    cfg = dict(graph=builder, num_periods=num_periods, backlog=backlog, alpha=alpha,
+               module="network_management", cls="NetInvMgmtMasterEnv", n_env=n_env, n_ep=n_ep,
+               ep_len=ep_len, base_seed=base_seed, topology=topo)
+    _save("net_graph_" + name, cfg, actions=actions, obs=obs, reward=rew, truncated=trunc,
+          reset_obs=reset_obs, **rec)
+
+
+def gen_graphs():
+    """Graphs outside the reference's built-in two (tests/net_graphs.py)."""
+    import warnings
+    warnings.simplefilter("ignore")
+    sys.path.insert(0, os.path.dirname(HERE))
+    import net_graphs
+    shape = {"mixed_2ep": dict(n_ep=2, base_seed=7100), "mixed_lost": dict(base_seed=7200),
+             "minimal": dict(base_seed=7300), "chain": dict(base_seed=7400),
+             "wide": dict(n_env=4, base_seed=7500)}
+    for name, (builder, T, backlog, alpha) in net_graphs.GOLDEN_CASES.items():
+        gen_net_graph(name, builder, T, backlog, alpha, **shape.get(name, {}))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "edges":
         gen_edges()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "graphs":
+        gen_graphs()
         return
     assert "/root/reference" in sys.path or any("reference" in p for p in sys.path), \
         "run with PYTHONPATH=tests/golden/standin:/root/reference"
