@@ -208,6 +208,9 @@ int invsim_status(invsim_handle *h, uint32_t *flags, int32_t clear);
  *                              poisson.ppf restated on device, newsvendor.hip nv_poisson_ppf)
  *   INVSIM_POLICY_SS           sSPolicyAgent  benchmark_newsvendor_sb3_rllib.py:363-371 (Newsvendor;
  *                              safety_factor carries S_buffer_factor)
+ *   INVSIM_POLICY_RANDOM       RandomAgent (env.action_space.sample() every step; the first
+ *                              agent of every benchmark_*.py list), any family and any graph:
+ *                              see "RandomAgent" below
  * CLASSIC_NV / SS need mu_max * (lead_time + 1) * max(1, safety_factor) <= 1e6 (INVSIM_ERANGE).
  * Per-env metrics (f64, accumulated with += so a caller may chain launches),
  * the sums evaluate_agent keeps (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -218,13 +221,15 @@ int invsim_status(invsim_handle *h, uint32_t *flags, int32_t clear);
  *   NetInvMgmt: [2] retail demand D  [3] retail sales S  [4] retail U[t+1]
  *               [5 + j] X[t+1] of main node j (j < n_main)
  *   Newsvendor: [0], [1] only
- * Unavailable with SAME_STEP autoreset and (NetInvMgmt) for graphs other than
- * the reference's default / custom ones (invsim_kernel_variant != 0). */
+ * Unavailable with SAME_STEP autoreset.  On NetInvMgmt graphs other than the
+ * reference's default / custom ones (invsim_kernel_variant == 0) the agents
+ * are CONSTANT and RANDOM. */
 #define INVSIM_POLICY_CONSTANT 1
 #define INVSIM_POLICY_BASE_STOCK 2
 #define INVSIM_POLICY_ORDER_UP_TO 3
 #define INVSIM_POLICY_CLASSIC_NV 4
 #define INVSIM_POLICY_SS 5
+#define INVSIM_POLICY_RANDOM 6
 #define INVSIM_POLICY_MAX_ACTION 32
 
 typedef struct {
@@ -232,7 +237,10 @@ typedef struct {
     int32_t variant;         /* CLASSIC_NV: 0 'k_vs_h', 1 'profit_margin'; else 0 */
     double safety_factor;    /* BASE_STOCK / ORDER_UP_TO / CLASSIC_NV; SS: S_buffer_factor */
     double mu;               /* BASE_STOCK: env.dist_param.get('mu', 10) as the agent reads it */
-    const void *constant;    /* CONSTANT: host array [action_dim] in the action dtype */
+    const void *constant;    /* CONSTANT: host array [action_dim] in the action dtype: the action.
+                              * RANDOM: host array [action_dim] in the action dtype: the action
+                              * space's upper bounds `high` (the field's second use).
+                              * Both: action_dim <= INVSIM_POLICY_MAX_ACTION (INVSIM_ERANGE) */
 } invsim_policy;
 
 int invsim_metrics_dim(const invsim_handle *h, int32_t *dim);
@@ -242,6 +250,44 @@ int invsim_metrics_dim(const invsim_handle *h, int32_t *dim);
  * agent took), metrics [N][invsim_metrics_dim] (+=).  Autoreset as set. */
 int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *policy, void *obs, double *reward,
                           uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream);
+
+/* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
+ * action_space, so its RandomAgent has no trajectory to match; the contract is
+ * numpy's Generator on a stream of the env's own:
+ *   generator  one PCG64 per env, separate from the demand generator, in a
+ *              caller-owned device buffer u64 [4][Npad] (invsim_action_rng_bytes;
+ *              rows state hi / state lo / inc hi / inc lo, as the `rng` state
+ *              field).  invsim_seed_action_rng gives env i
+ *              SeedSequence(base + first_index + i); invsim's Python layer uses
+ *              base = 2**64 + seed (base_hi = 1), so the actions of seed s do not
+ *              replay the demand uniforms of reset(seed=s).  Checkpointing the
+ *              stream is cloning the buffer; the handle's arena and state blob
+ *              do not hold it.
+ *   draws      one launch step of one env consumes exactly action_dim doubles
+ *              u = (next_uint64 >> 11) * 2**-53 in action-index order, whether
+ *              or not the step is applied (a NEXT_STEP reset step and a step
+ *              refused past the horizon draw too): K launch steps advance
+ *              every generator by K * action_dim doubles.
+ *   actions    f32 spaces (Newsvendor, NetInvMgmt): (float)((double)high[a] * u)
+ *              int64 spaces (InvMgmt): (int64)floor((double)(high[a] + 1) * u)
+ *              i.e. Generator.uniform(0, high) / uniform(0, high + 1) floored.
+ *   recorded   `actions` of invsim_rollout_policy holds the drawn action of
+ *              every step, reset steps included (the other agents leave those
+ *              rows unwritten), and equals what invsim_sample_actions writes.
+ * The action stream is PCG64 under both demand streams and never touches the
+ * `rng` rows or philox_step.  The generators are device-resident, so a captured
+ * launch continues the stream at every replay.
+ * invsim_set_action_rng attaches the buffer to h (NULL detaches; not during
+ * capture); a RANDOM rollout or invsim_sample_actions without one returns
+ * INVSIM_EINVAL.  invsim_sample_actions draws K steps of actions [K][N][A]
+ * (action dtype) from the attached generators and advances them: random
+ * actions for callers who feed invsim_step / invsim_rollout themselves. */
+int invsim_action_rng_bytes(const invsim_handle *h, int64_t *bytes);
+int invsim_seed_action_rng(invsim_handle *h, uint64_t *arng, uint64_t base_lo, uint64_t base_hi,
+                           int64_t first_index, void *stream);
+int invsim_set_action_rng(invsim_handle *h, uint64_t *arng);
+int invsim_sample_actions(invsim_handle *h, int32_t K, const void *high, void *actions /* [K][N][A] */,
+                          void *stream);
 
 /* Episodic-return statistics of K steps of outputs, the reduction the
  * reference's evaluation harness keeps per episode (episode_rewards ->

@@ -81,6 +81,8 @@ struct invsim_handle {
     int32_t cap_t_cur = 0;
     int cap_la_slot = 0;
     int64_t cap_steps = 0;
+    // RandomAgent's action generators (invsim_set_action_rng): caller-owned u64 [4][Npad], or null
+    uint64_t *arng = nullptr;
     std::string err;
 };
 
@@ -1076,6 +1078,26 @@ int invsim_metrics_dim(const invsim_handle *h, int32_t *dim) {
     return INVSIM_OK;
 }
 
+// the RANDOM kind's PolicyIO fields: the upper bounds `high` (host, [action_dim]
+// in the action dtype) and the attached action generators
+static int random_policy(invsim_handle *h, const void *high, PolicyIO &p, bool rollout) {
+    if (!high) return fail(h, INVSIM_EINVAL, "RANDOM policy needs the action space's upper bounds");
+    if (h->act_dim > POL_MAX_A) return fail(h, INVSIM_ERANGE, "action_dim too large for a RANDOM policy");
+    if (rollout && h->family == INVSIM_NETINVMGMT && !h->net_spec && net_random_lds_bytes(h->net) > 160 * 1024)
+        return fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch of a RANDOM policy rollout "
+                                      "(the generic kernel keeps the drawn actions of 64 envs in LDS)");
+    if (!h->arng)
+        return fail(h, INVSIM_EINVAL, "no action generators attached: seed a buffer with invsim_seed_action_rng and "
+                                      "attach it with invsim_set_action_rng");
+    p.kind = POL_RANDOM;
+    p.arng = h->arng;
+    for (int a = 0; a < h->act_dim; a++) {
+        if (h->family == INVSIM_INVMGMT) p.ci[a] = ((const int64_t *)high)[a];
+        else p.cf[a] = ((const float *)high)[a];
+    }
+    return INVSIM_OK;
+}
+
 int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *policy, void *obs, double *reward,
                           uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream) {
     TraceRange tr_("invsim_rollout_policy");
@@ -1122,10 +1144,57 @@ int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *poli
                 return fail(h, INVSIM_ERANGE, "critical-ratio policies need mu_max * (lead_time + 1) * safety_factor <= 1e6");
             break;
         }
+        case INVSIM_POLICY_RANDOM:
+            if (int rc = random_policy(h, policy->constant, p, true)) return rc;
+            break;
         default: return fail(h, INVSIM_EINVAL, "unknown policy kind");
     }
     DeviceGuard g(h->device);
     return run_steps(h, K, nullptr, obs, reward, terminated, truncated, nullptr, (hipStream_t)stream, &p);
+}
+
+int invsim_action_rng_bytes(const invsim_handle *h, int64_t *bytes) {
+    if (!h || !bytes) return fail(nullptr, INVSIM_EINVAL, "null argument");
+    *bytes = 4 * h->Npad * (int64_t)sizeof(uint64_t);
+    return INVSIM_OK;
+}
+
+int invsim_seed_action_rng(invsim_handle *h, uint64_t *arng, uint64_t base_lo, uint64_t base_hi, int64_t first,
+                           void *stream) {
+    TraceRange tr_("invsim_seed_action_rng");
+    if (!h || !arng) return fail(h, INVSIM_EINVAL, "null argument");
+    if (first < 0) return fail(h, INVSIM_EINVAL, "first_index must be >= 0");
+    if (int rc = capture_check(h, (hipStream_t)stream)) return rc;
+    DeviceGuard g(h->device);
+    // seed_range_kernel over the caller's rows: the demand generators, their
+    // lookahead cache and the fast stream's counter are not touched
+    Common c = h->cm;
+    c.rng = act_rng_rows(arng, h->Npad);
+    c.u32buf = nullptr;
+    hipError_t e = seed_range_launch(c, base_lo, base_hi, first, nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "seed_action_rng launch");
+}
+
+int invsim_set_action_rng(invsim_handle *h, uint64_t *arng) {
+    if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
+    if (int rc = refuse_in_capture(h, "set_action_rng")) return rc;
+    h->arng = arng;
+    return INVSIM_OK;
+}
+
+int invsim_sample_actions(invsim_handle *h, int32_t K, const void *high, void *actions, void *stream) {
+    TraceRange tr_("invsim_sample_actions");
+    if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
+    if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
+    if (K == 0) return INVSIM_OK;
+    if (h->N && !actions) return fail(h, INVSIM_EINVAL, "null output/input buffer");
+    PolicyIO p{};
+    if (int rc = random_policy(h, high, p, false)) return rc;   // (no LDS check: sample_actions_kernel uses none)
+    if (int rc = capture_check(h, (hipStream_t)stream)) return rc;
+    p.act_out = actions;
+    DeviceGuard g(h->device);
+    hipError_t e = sample_actions_launch(p, h->family == INVSIM_INVMGMT, K, h->N, h->Npad, h->act_dim, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "sample_actions launch");
 }
 
 int invsim_episode_fold(const double *reward, const uint8_t *terminated, const uint8_t *truncated, int32_t K,

@@ -44,6 +44,27 @@ __global__ void __launch_bounds__(256) period_fill_kernel(Common cm, int32_t t) 
     if (e < cm.N) cm.period[e] = t;
 }
 
+// invsim_sample_actions: K launch steps of RandomAgent draws (act_draw) for
+// every env, one thread per env: the generator is loaded once, advanced
+// K * A doubles and stored once -- what a RANDOM policy rollout of K steps
+// draws and records.  A: action entries per env (<= POL_MAX_A).
+template <typename T>
+__global__ void __launch_bounds__(256)
+sample_actions_kernel(PolicyIO pol, int32_t K, int64_t N, int64_t Npad, int32_t A, T *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    ActGen ag;
+    ag.load(pol, Npad, e);
+    for (int k = 0; k < K; k++) {
+        T *row = out + ((int64_t)k * N + e) * A;
+        for (int a = 0; a < A; a++) {
+            if constexpr (sizeof(T) == 8) out_store(row + a, act_draw(ag.g, pol.ci[a]));
+            else out_store(row + a, act_draw(ag.g, pol.cf[a]));
+        }
+    }
+    ag.store(pol, Npad, e);
+}
+
 // A masked reset with an episode sink set: the reset envs abandon their
 // episode, so their running return restarts at +0.0 like the harness's
 // `episode_reward = 0.0` at every reset (benchmark_InvManagementBacklogEnv.py:
@@ -192,6 +213,15 @@ hipError_t seed_words_launch(const Common &cm, const uint32_t *words, const int3
     if (cm.N == 0) return hipSuccess;
     hipLaunchKernelGGL(seed_words_kernel, dim3(grid_for(cm.N, 256)), dim3(256), 0, s, cm, words,
                        nwords, mask);
+    return hipGetLastError();
+}
+
+hipError_t sample_actions_launch(const PolicyIO &pol, bool i64, int32_t K, int64_t N, int64_t Npad, int32_t A,
+                                 hipStream_t s) {
+    if (N == 0 || K <= 0) return hipSuccess;
+    const dim3 grid(grid_for(N, 256)), block(256);
+    if (i64) hipLaunchKernelGGL(sample_actions_kernel<int64_t>, grid, block, 0, s, pol, K, N, Npad, A, (int64_t *)pol.act_out);
+    else hipLaunchKernelGGL(sample_actions_kernel<float>, grid, block, 0, s, pol, K, N, Npad, A, (float *)pol.act_out);
     return hipGetLastError();
 }
 

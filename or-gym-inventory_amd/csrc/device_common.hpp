@@ -527,4 +527,29 @@ struct RngSoA {
     __device__ __forceinline__ void store_state(int64_t, const PhiloxGen &) const {}
 };
 
+// ---------------------------------------------------------------- RandomAgent
+// The reference's RandomAgent is env.action_space.sample() every step; its
+// contract here (include/invsim.h, INVSIM_POLICY_RANDOM) is numpy's
+// Generator.uniform(0, high) on a PCG64 stream of the env's own, separate from
+// the demand generator: one double u = (next_uint64 >> 11) * 2^-53 per action
+// entry, in action-index order, every launch step.  The product is taken in
+// f64 and then converted (this file is built with -ffp-contract=off: the
+// multiply and the conversion stay two roundings, as numpy's).
+//   f32 action spaces (Newsvendor, NetInvMgmt):  (float)((double)high * u)
+//   int64 action spaces (InvMgmt):               (int64)floor((double)(high + 1) * u)
+__device__ __forceinline__ float act_draw(Pcg &g, float high) {
+    const double v = (double)high * g.next_double();
+    return (float)v;
+}
+__device__ __forceinline__ int64_t act_draw(Pcg &g, int64_t high) {
+    const double v = (double)(high + 1) * g.next_double();
+    return (int64_t)floor(v);
+}
+
+// The action generators: a caller-owned u64 [4][Npad] buffer laid out as the
+// `rng` state field (rows state hi / state lo / inc hi / inc lo)
+__host__ __device__ inline RngSoA act_rng_rows(uint64_t *arng, int64_t npad) {
+    return RngSoA{arng, arng + npad, arng + 2 * npad, arng + 3 * npad};
+}
+
 }  // namespace invsim

@@ -26,6 +26,22 @@
 // K) with PCG64, I, B and the period in registers.
 #include "kernels.hpp"
 
+// invmgmt_rnd.hip compiles this file with INVSIM_IM_RND_TU: every policy kernel
+// instantiated there is the RANDOM (RandomAgent) variant (kernels.hpp ActGen),
+// whose dynamics code draws each launch step's order from the env's action
+// generator -- before the reset / overrun branches, so every launch step
+// draws -- instead of asking an agent.  Without the macro this file is the
+// text it was: the other translation units' kernels do not change.
+#ifdef INVSIM_IM_RND_TU
+#define IM_RND 1
+#define IM_RND_PARAM , ActGen &ag
+#define IM_RND_ARG , ag
+#else
+#define IM_RND 0
+#define IM_RND_PARAM
+#define IM_RND_ARG
+#endif
+
 namespace invsim {
 namespace {
 
@@ -473,7 +489,7 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
                                                ImState<M1, BACKLOG, G> &st, int &t, bool &fault,
                                                int64_t *tile, int64_t *trow, const double *rhs,
                                                TableStage *ts, const double *pre_apow, const int64_t *pre_udem,
-                                               const PolicyIO &pol, double *met) {
+                                               const PolicyIO &pol, double *met IM_RND_PARAM) {
     const int j = lane & (LPE - 1);
     const bool leader = j == 0;
     const int64_t N = P.cm.N;
@@ -484,6 +500,15 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
     double rew = 0.0;
     int64_t dem = 0;
     ImPending<M1> pend;
+#if IM_RND
+    int64_t ract[M1];
+#pragma unroll
+    for (int i = 0; i < M1; i++) ract[i] = act_draw(ag.g, pol.ci[i]);
+    if (valid && leader && pol.act_out) {
+#pragma unroll
+        for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, ract[i]);
+    }
+#endif
     if (!STEP_ONLY && ts) {   // all lanes write the table before the divergent branch
         ts->flush(lane);
         ts = nullptr;
@@ -512,6 +537,9 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
         const int64_t udem = pre_udem ? *pre_udem : P.user_D[t];
         const int64_t *arow = io.act + ea * M1;
         int64_t pact[M1];
+#if IM_RND
+        arow = ract;
+#else
         if (POL) {
             if (pol.kind == POL_BASE_STOCK) {
                 im_base_stock<M1, BACKLOG>(P, pol, st, t, e, pact);
@@ -525,6 +553,7 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
             }
             arow = pact;
         }
+#endif
         tr = im_step_regs<M1, BACKLOG, NPD>(P, e, valid, j, t, st, arow, trow, rhs, ts, apow, udem, r, d,
                                             POL ? met : nullptr,
                                             (valid && leader && k == io.K - 1) ? (int64_t *)P.cm.info_rec : nullptr,
@@ -631,19 +660,23 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     for (int q = 0; q <= M1; q++) st.B[q] = BACKLOG ? P.B[q * S + e] : 0;
     int t = t0;
     bool fault = false;
+#if IM_RND
+    ActGen ag;
+    ag.load(pol, S, valid ? e : N - 1);
+#endif
     constexpr int MD = 6;                       // metrics (invsim.h INVSIM_METRICS_*)
     double met[MD];
 #pragma unroll
     for (int q = 0; q < MD; q++) met[q] = (POL && pol.metrics) ? pol.metrics[(valid ? e : N - 1) * MD + q] : 0.0;
     if (ONE) {
         im_launch_step<M1, BACKLOG, TU, false, NPD>(P, io, 0, e, e0, lane, valid, nvalid, st, t, fault, im_tile, trow,
-                                               rhs_l, &ts, &apow0, &udem0, pol, met);
+                                               rhs_l, &ts, &apow0, &udem0, pol, met IM_RND_ARG);
     } else {
         ts.flush(lane);
         for (int k = 0; k < io.K; k++) {
             st.g.set_step(P.cm.ph_step + (uint64_t)k);
             im_launch_step<M1, BACKLOG, false, POL, NPD>(P, io, k, e, e0, lane, valid, nvalid, st, t, fault, im_tile,
-                                                    trow, rhs_l, nullptr, nullptr, nullptr, pol, met);
+                                                    trow, rhs_l, nullptr, nullptr, nullptr, pol, met IM_RND_ARG);
         }
     }
     if (valid && leader) {
@@ -661,6 +694,9 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
+#if IM_RND
+        ag.store(pol, S, e);
+#endif
     }
     TWAIT();
     TPROBE(5);
@@ -1357,6 +1393,10 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
     double napow = P.alpha_pow[t < P.periods ? t : 0];   // alpha**t of the next step, prefetched
     int64_t dlast = 0;
     bool last_real = false;
+#if IM_RND
+    ActGen ag;
+    ag.load(pol, S, el);
+#endif
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
     // the group's partials are read only after the loop (they would hold 8
     // VGPRs through it: the policy kernel then needs AGPRs, one wave per SIMD)
@@ -1373,6 +1413,14 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
             int64_t req[M1];
 #pragma unroll
             for (int i = 0; i < M1; i++) req[i] = nact[i];
+#if IM_RND
+#pragma unroll
+            for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
+            if (valid && pol.act_out) {
+#pragma unroll
+                for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+            }
+#endif
             const double apow = napow;
             {
                 const int tn = (t >= P.periods) ? 0 : t + 1;     // the next launch step's period
@@ -1398,7 +1446,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                 t = 0;
             } else {
                 const int64_t d = db[kk * WAVE + lane];
-                if (POL) {
+                if (POL && !IM_RND) {
                     if (pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register windows
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
@@ -1527,6 +1575,9 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
         if (ep_part) P.cm.ep_ret[e] = ep.r;
+#if IM_RND
+        if (POL) ag.store(pol, S, e);
+#endif
     }
     if (ep_part) {
         EpPart epp;
@@ -1753,6 +1804,10 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     for (int i = 0; i < M1; i++) nact[i] = POL ? 0 : io.act[el * M1 + i];
     int64_t dlast = 0;
     bool last_real = false;
+#if IM_RND
+    ActGen ag;
+    ag.load(pol, S, el);
+#endif
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
     // the group's partials are read only after the loop (they would hold 8
     // VGPRs through it: the policy kernel then needs AGPRs, one wave per SIMD)
@@ -1771,6 +1826,14 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
             int64_t req[M1];
 #pragma unroll
             for (int i = 0; i < M1; i++) req[i] = nact[i];
+#if IM_RND
+#pragma unroll
+            for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
+            if (valid && pol.act_out) {
+#pragma unroll
+                for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+            }
+#endif
             if (!POL && k + 1 < K) {    // prefetch the next step's actions
 #pragma unroll
                 for (int i = 0; i < M1; i++) nact[i] = io.act[((int64_t)(k + 1) * N + el) * M1 + i];
@@ -1792,7 +1855,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                 t = 0;
             } else {
                 const int64_t d = db[kk * WAVE + lane];
-                if (POL) {
+                if (POL && !IM_RND) {
                     if (pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register history
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
@@ -1888,6 +1951,9 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
         if (ep_part) P.cm.ep_ret[e] = ep.r;
+#if IM_RND
+        if (POL) ag.store(pol, S, e);
+#endif
     }
     if (ep_part) {
         EpPart epp;
@@ -1928,7 +1994,8 @@ inline bool im_sink_noop(const ImParams &p, int t_u, const PolicyIO *pol, const 
 // (open loop, or the in-kernel BaseStock / ConstantOrder agents)
 inline bool im_roll_applies(const ImParams &p, int M1, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io) {
-    const bool pol_roll = pol && (pol->kind == POL_BASE_STOCK || pol->kind == POL_CONSTANT) && p.cm.kn.im_pol_roll;
+    const bool pol_roll = pol && (pol->kind == POL_BASE_STOCK || pol->kind == POL_CONSTANT || pol->kind == POL_RANDOM) &&
+                          p.cm.kn.im_pol_roll;
     return (!pol || pol_roll) && io.K > 1 && t_u >= 0 && p.cm.autoreset != AR_SAME_STEP && p.dist == 1 &&
            !p.cm.info_rec && M1 == 3 && p.L[0] == 1 && p.L[1] == 5 && p.L[2] == 10 && p.lt_max == 10 &&
            p.cm.kn.im_roll;
@@ -1974,8 +2041,10 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
         if (backlog) R_(true, true);
         else R_(false, true);
     } else {
+#if !IM_RND
         if (backlog) R_(true, false);
         else R_(false, false);
+#endif
     }
 #undef R_
     return hipGetLastError();
@@ -2099,6 +2168,10 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
     // lock-step rollout of the reference's default lead times: register windows
     // and a demand wave (im_roll3_kernel / im_roll3o_kernel), open loop or with
     // the in-kernel BaseStock / ConstantOrder agents
+#if !IM_RND
+    // RANDOM: the same rows, from the RND translation unit (invmgmt_rnd.hip)
+    if (pol && pol->kind == POL_RANDOM) return im_rnd_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
+#endif
     if (im_roll_applies(p, M1, t_u, pol, io)) {
         sunk = true;                  // so do the rollout kernels
         return im_roll_launch<RG>(p, backlog, t_u, pol, io, s);
@@ -2131,7 +2204,43 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
 
 }  // namespace
 
-#ifdef INVSIM_IM_FAST_TU
+#if IM_RND
+// invmgmt_rnd.hip: this file compiled a third time, for the RANDOM variants of
+// the policy kernels of both demand streams: im_roll3o_kernel / im_roll3_kernel
+// where im_roll_applies (the rows of BaseStock / ConstantOrder),
+// im_run_kernel otherwise.
+template <class RG>
+static hipError_t im_rnd_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                                   const StepIO<int64_t, int64_t> &io, bool &sunk, hipStream_t s) {
+    if (im_roll_applies(p, M1, t_u, &pol, io)) {
+        sunk = true;
+        return im_roll_launch<RG>(p, backlog, t_u, &pol, io, s);
+    }
+    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
+    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
+    const bool npd = p.dist >= 2 && p.dist <= 4;
+#define KR_(M, B, TU, NPD) hipLaunchKernelGGL((im_run_kernel<M, B, TU, false, true, NPD, RG>), grid, block, lds, s, p, t_u, io, pol)
+#define L_(M, B)                                \
+    do {                                        \
+        if (t_u >= 0) {                         \
+            if (npd) KR_(M, B, true, true);     \
+            else KR_(M, B, true, false);        \
+        } else {                                \
+            if (npd) KR_(M, B, false, true);    \
+            else KR_(M, B, false, false);       \
+        }                                       \
+    } while (0)
+    IM_DISPATCH(M1, backlog, L_)
+#undef L_
+#undef KR_
+    return hipGetLastError();
+}
+hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
+    if (philox) return im_rnd_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, sunk, s);
+    return im_rnd_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, sunk, s);
+}
+#elif defined(INVSIM_IM_FAST_TU)
 // invmgmt_ph.hip: this file compiled a second time for the fast-stream
 // kernels (a TU of their own, so the two instantiation sets compile in parallel)
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
@@ -2168,7 +2277,7 @@ INVSIM_PTRS_STATS_TU(im)
 
 }  // namespace invsim
 
-#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU)
+#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND
 extern "C" int invsim_debug_timing(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbuf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }

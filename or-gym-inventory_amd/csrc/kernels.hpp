@@ -393,18 +393,43 @@ struct StepIO {
 // in the kernel from the env state by a restated heuristic agent, every output
 // is optional, and per-env evaluation metrics accumulate in registers.
 enum { POL_NONE = 0, POL_CONSTANT = 1, POL_BASE_STOCK = 2, POL_ORDER_UP_TO = 3, POL_CLASSIC_NV = 4,
-       POL_SS = 5 };
+       POL_SS = 5, POL_RANDOM = 6 };
 constexpr int POL_MAX_A = 32;
 struct PolicyIO {
     int32_t kind;
     int32_t mdim;             // metrics per env (0: none)
     int32_t variant;          // CLASSIC_NV: 0 'k_vs_h', 1 'profit_margin'
     int32_t pad_;
-    double sf, mu;            // safety factor (SS: S_buffer_factor); BASE_STOCK demand mean
-    int64_t ci[POL_MAX_A];    // CONSTANT actions, int64 action spaces
-    float cf[POL_MAX_A];      // CONSTANT actions, f32 action spaces
+    double sf;                // safety factor (SS: S_buffer_factor)
+    union {                   // (one slot: the struct keeps the size every policy kernel's arguments had)
+        double mu;            // BASE_STOCK: demand mean
+        uint64_t *arng;       // RANDOM: the action generators [4][Npad] (act_rng_rows)
+    };
+    int64_t ci[POL_MAX_A];    // CONSTANT actions (RANDOM: the upper bounds), int64 action spaces
+    float cf[POL_MAX_A];      // CONSTANT actions (RANDOM: the upper bounds), f32 action spaces
     void *act_out;            // [K][N][action_dim] actions taken, may be null
     double *metrics;          // [N][mdim], accumulated (+=), may be null
+};
+static_assert(sizeof(PolicyIO) == 32 + POL_MAX_A * 12 + 16, "a by-value argument of every policy kernel");
+
+// RANDOM (RandomAgent) is a compile-time variant, RND, of the run kernels and of
+// the fused rollout kernels (their dynamics waves draw); for InvMgmt the variant
+// is a translation unit, invmgmt_rnd.hip (INVSIM_IM_RND_TU), not a template
+// argument, so invmgmt.o's kernels are the text they were: the
+// action generator's four registers stay live across a launch's K steps, and
+// the other agents' instantiations (RND = false) must not pay for them.  A RND
+// kernel loads the env's action generator once, draws action_dim doubles every
+// launch step -- applied or not: a NEXT_STEP reset step and a step refused
+// past the horizon draw too -- records the drawn action of every step in
+// act_out, and stores the generator state once at the end.
+struct ActGen {
+    Pcg g;
+    __device__ __forceinline__ void load(const PolicyIO &pol, int64_t npad, int64_t e) {
+        g = act_rng_rows(pol.arng, npad).load(e);
+    }
+    __device__ __forceinline__ void store(const PolicyIO &pol, int64_t npad, int64_t e) const {
+        act_rng_rows(pol.arng, npad).store_state(e, g);
+    }
 };
 
 // Lock-step period: when every env of the handle is at the same period the host
@@ -613,6 +638,10 @@ hipError_t seed_range_launch(const Common &cm, uint64_t base_lo, uint64_t base_h
 hipError_t seed_words_launch(const Common &cm, const uint32_t *words, const int32_t *nwords,
                              const uint8_t *mask, hipStream_t s);
 hipError_t period_fill_launch(const Common &cm, int32_t t, hipStream_t s);
+// K steps of RandomAgent draws from the generators `arng` [4][Npad] into
+// actions [K][N][A] (int64 or f32: `i64`); high: the policy's ci / cf bounds
+hipError_t sample_actions_launch(const PolicyIO &pol, bool i64, int32_t K, int64_t N, int64_t Npad, int32_t A,
+                                 hipStream_t s);
 hipError_t episode_fold_launch(const double *rew, const uint8_t *term, const uint8_t *trunc, int32_t K,
                                int64_t N, double *ret, double *acc, hipStream_t s);
 // the EpSink fold of K output rows into per-group partials (no atomics)
@@ -644,6 +673,10 @@ hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool 
 // fast stream's demand-only lookahead cache (never committed: it holds no state)
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s);
+// the RANDOM (RND) instantiations of im_run_kernel, invmgmt_rnd.hip (both demand streams)
+// (the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
+hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
 // cm.rng <- the committed generator state held by the lookahead cache (whose
 // current slot is `slot`); needed before anything reads cm.rng while it is valid
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s);
@@ -659,5 +692,6 @@ hipError_t net_reset_launch(const NetParams &p, const uint8_t *mask, float *obs,
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
                           hipStream_t s);
 size_t net_lds_bytes(const NetParams &p);
+size_t net_random_lds_bytes(const NetParams &p);   // net_run_kernel's RANDOM variant
 
 }  // namespace invsim

@@ -37,6 +37,11 @@ __device__ __forceinline__ NetScratch scratch_of(const NetParams &P, double *bas
     return s;
 }
 __host__ __device__ inline int scratch_rows(int J, int E, int RL) { return 3 * J + 3 * E + 3 * RL; }
+// the obs tile [EPW][O] f32 behind the scratch rows, padded to 16 B
+__host__ __device__ inline size_t net_tile_bytes(const NetParams &p) {
+    const size_t tile = (size_t)EPW * (p.RL + p.J + p.sumL) * sizeof(float);
+    return (tile + 15) / 16 * 16;
+}
 
 #define LV(a, i) (a)[(i) * WAVE]
 
@@ -208,7 +213,11 @@ __device__ bool net_step_lds(const NetParams &P, int64_t e, int gl, int t, RG &g
 // (ConstantOrderAgent, benchmark_NetInvMgmtBacklogEnv.py:119-135) on any graph:
 // every output optional, evaluate_agent metrics (as net_spec_kernel) summed
 // into pol.metrics in place.
-template <bool TU, bool POL, class RG>
+// RND (POL_RANDOM, kernels.hpp ActGen): the reorder quantities of every launch
+// step are drawn from the env's action generator into the lane's row of an
+// LDS block behind the obs tile (net_act_lds_bytes), which the step reads as
+// its action row.
+template <bool TU, bool POL, class RG, bool RND = false>
 __global__ void __launch_bounds__(WAVE)
 net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) double net_lds[];
@@ -227,11 +236,16 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     float *tile = reinterpret_cast<float *>(net_lds + (int64_t)rows * WAVE);
     float *trow = tile + (int64_t)(lane / LPE) * O;
 
+    float *arow = reinterpret_cast<float *>(reinterpret_cast<char *>(tile) + net_tile_bytes(P)) +
+                  (int64_t)(lane / LPE) * P.E;
+
     RG g;
+    ActGen ag;
     uint64_t u32 = 0;         // numpy's buffered 32-bit half (integers markets)
     int t = t_u;
     if (valid) {
         P.cm.rng.load(e, g);
+        if constexpr (RND) ag.load(pol, S, e);
         if (P.cm.u32buf && !RG::kCounter) u32 = P.cm.u32buf[e];
         for (int j = 0; j < P.J; j++) LV(s.X, j) = P.X[j * S + e];
         for (int r = 0; r < P.RL; r++) LV(s.U, r) = P.U[r * S + e];
@@ -244,6 +258,13 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
         bool tr = false;
         g.set_step(P.cm.ph_step + (uint64_t)k);
         if (valid) {
+            if constexpr (RND) {
+                for (int q = 0; q < P.E; q++) {
+                    const float a = act_draw(ag.g, pol.cf[q]);
+                    arow[q] = a;      // every lane of the env writes the row it reads (the same value)
+                    if (leader && pol.act_out) ((float *)pol.act_out)[oi * P.E + q] = a;
+                }
+            }
             if (t >= P.T) {
                 if (P.cm.autoreset == AR_NEXT_STEP) {
                     net_reset_lds(P, s, leader ? trow : nullptr);
@@ -259,7 +280,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             } else {
                 double r;
                 if (RG::kCounter) u32 = 0;          // fast stream: no half carried between steps
-                tr = net_step_lds(P, e, gl, t, g, u32, s, POL ? pol.cf : io.act + oi * P.E, trow, r,
+                tr = net_step_lds(P, e, gl, t, g, u32, s, RND ? arow : POL ? pol.cf : io.act + oi * P.E, trow, r,
                                   k == io.K - 1 ? P.cm.info_demand : nullptr,
                                   k == io.K - 1 ? (double *)P.cm.info_rec : nullptr);
                 if (leader && (!POL || io.rew)) {
@@ -268,7 +289,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
                     io.trunc[oi] = tr ? 1 : 0;
                 }
                 if (POL && leader) {
-                    if (pol.act_out)
+                    if (!RND && pol.act_out)
                         for (int q = 0; q < P.E; q++) ((float *)pol.act_out)[oi * P.E + q] = pol.cf[q];
                     if (pol.metrics) {   // evaluate_agent metrics (benchmark_NetInvMgmtLostSalesEnv.py:264-300)
                         double *met = pol.metrics + e * (5 + P.J);
@@ -311,6 +332,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
         for (int k = 0; k < P.E; k++) P.Y[k * S + e] = LV(s.Y, k);
         if (!TU) P.cm.period[e] = t;
         if (fault) atomicOr(P.cm.status, 1u);
+        if constexpr (RND) ag.store(pol, S, e);
     }
 }
 
@@ -340,9 +362,10 @@ inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / b
 }  // namespace
 
 size_t net_lds_bytes(const NetParams &p) {
-    const size_t tile = (size_t)EPW * (p.RL + p.J + p.sumL) * sizeof(float);
-    return (size_t)scratch_rows(p.J, p.E, p.RL) * WAVE * sizeof(double) + (tile + 15) / 16 * 16;
+    return (size_t)scratch_rows(p.J, p.E, p.RL) * WAVE * sizeof(double) + net_tile_bytes(p);
 }
+// the RND variant's: + action rows [EPW][E] f32 behind the obs tile
+size_t net_random_lds_bytes(const NetParams &p) { return net_lds_bytes(p) + (size_t)EPW * p.E * sizeof(float); }
 
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
                           hipStream_t s) {
@@ -352,7 +375,20 @@ hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, cons
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
     PolicyIO none{};
     const PolicyIO &pv = pol ? *pol : none;
-    if (pol && pol->kind != POL_CONSTANT) return hipErrorInvalidValue;
+    if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM) return hipErrorInvalidValue;
+    if (pol && pol->kind == POL_RANDOM) {
+        const size_t ldr = net_random_lds_bytes(p);
+        if (ldr > 160 * 1024) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first, INVSIM_ERANGE)
+#define KR_(TU)                                                                                        \
+    do {                                                                                               \
+        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, true>), grid, block, ldr, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, true>), grid, block, ldr, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KR_(true);
+        else KR_(false);
+#undef KR_
+        return hipGetLastError();
+    }
 #define K_(TU, POL)                                                                                    \
     do {                                                                                               \
         if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, POL, PhiloxGen>), grid, block, lds, s, p, t_u, io, pv); \

@@ -296,7 +296,9 @@ __device__ __forceinline__ void spec_shift(NetSt<G, RG> &s, const double (&Rn)[G
     }
 }
 
-template <class G, bool TU, bool ONE, bool POL, class RG>
+// RND (POL_RANDOM, kernels.hpp ActGen): the reorder quantities are drawn from
+// the env's action generator at the top of every launch step.
+template <class G, bool TU, bool ONE, bool POL, class RG, bool RND = false>
 __global__ void __launch_bounds__(WAVE)
 net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) float ns_lds[];
@@ -383,6 +385,8 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     bool fault = false;
     bool dirty_all = false;                    // rollout: whole ring rewritten at the end
     const int t_start = t;
+    ActGen ag;
+    if constexpr (RND) ag.load(pol, S, el);
     double Rn[G::E];
 #pragma unroll
     for (int k = 0; k < G::E; k++) Rn[k] = 0.0;
@@ -397,6 +401,14 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
                 for (int k = 0; k < G::E; k++) act[k] = io.act[ea * G::E + k];
             }
             apow = P.alpha_pow[(t < P.T) ? t : 0];
+        }
+        if constexpr (RND) {
+#pragma unroll
+            for (int k = 0; k < G::E; k++) act[k] = act_draw(ag.g, pol.cf[k]);
+            if (valid && pol.act_out) {
+#pragma unroll
+                for (int k = 0; k < G::E; k++) out_store((float *)pol.act_out + oi * G::E + k, act[k]);
+            }
         }
         bool tr = false;
         if (!(ONE && TU) && t >= P.T) {
@@ -421,7 +433,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             if (POL) {
                 met[0] += r;                    // episode_reward += reward
                 met[1] += 1.0;
-                if (valid && pol.act_out) {
+                if (!RND && valid && pol.act_out) {
 #pragma unroll
                     for (int k = 0; k < G::E; k++) out_store((float *)pol.act_out + oi * G::E + k, act[k]);
                 }
@@ -491,6 +503,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
+        if constexpr (RND) ag.store(pol, S, e);
     }
     (void)t_start;
 }
@@ -1132,7 +1145,10 @@ struct NetRoll3 {
 // agent's fixed order instead of loading actions, every output is optional,
 // and the evaluate_agent sums accumulate in registers (spec_core, as
 // net_spec_kernel).
-template <class G, int CH_, bool POL, class RG = Pcg>
+// RND (POL_RANDOM, kernels.hpp ActGen): the dynamics wave draws each launch
+// step's reorder quantities from the env's action generator, reset steps
+// included; the demand wave and its ring are as for ConstantOrder.
+template <class G, int CH_, bool POL, class RG = Pcg, bool RND = false>
 __global__ void __launch_bounds__(3 * WAVE)
 net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
     using R3 = NetRoll3<G, CH_>;
@@ -1277,6 +1293,8 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
     for (int r = 0; r < RL; r++) dlast[r] = 0.0;
     bool last_real = false;
     double Rn[G::E];
+    ActGen ag;
+    if constexpr (RND) ag.load(pol, S, el);
     net_wg_sync();   // barrier 0: demand chunk 0 ready
     for (int c = 0; c < nch; c++) {
         const double *db = dbuf + (c % RD) * CH * RL * WAVE;
@@ -1295,6 +1313,14 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
             if (!POL && k + 1 < K) {                            // the next step's actions
 #pragma unroll
                 for (int q = 0; q < G::E; q++) nact[q] = io.act[((int64_t)(k + 1) * N + el) * G::E + q];
+            }
+            if constexpr (RND) {
+#pragma unroll
+                for (int q = 0; q < G::E; q++) act[q] = act_draw(ag.g, pol.cf[q]);
+                if (valid && pol.act_out) {
+#pragma unroll
+                    for (int q = 0; q < G::E; q++) out_store((float *)pol.act_out + oi * G::E + q, act[q]);
+                }
             }
             if (t >= P.T) {                                     // NEXT_STEP autoreset (:301-332)
 #pragma unroll
@@ -1326,7 +1352,7 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
                 if (POL) {
                     met[0] += rw;                                       // episode_reward += reward
                     met[1] += 1.0;
-                    if (valid && pol.act_out) {
+                    if (!RND && valid && pol.act_out) {
 #pragma unroll
                         for (int q = 0; q < G::E; q++) out_store((float *)pol.act_out + oi * G::E + q, act[q]);
                     }
@@ -1380,6 +1406,7 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
+        if constexpr (RND) ag.store(pol, S, e);
     }
 }
 
@@ -1759,7 +1786,8 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
         else hipLaunchKernelGGL((net_spec_kernel<G, TU, ONE, POL, Pcg>), grid, block, lds, s, p, t_u, io, pv);         \
     } while (0)
     // ... and the in-kernel ConstantOrder agent on the 3-role kernel
-    const bool pol_roll = pol && pol->kind == POL_CONSTANT && p.cm.kn.net_pol_roll;
+    const bool rnd = pol && pol->kind == POL_RANDOM;
+    const bool pol_roll = pol && (pol->kind == POL_CONSTANT || rnd) && p.cm.kn.net_pol_roll;
     if ((!pol || pol_roll) && io.K > 1 && t_u >= 0 && !p.cm.info_rec && p.cm.kn.net_roll &&
         (p.cm.autoreset == AR_NEXT_STEP || (p.cm.autoreset == AR_DISABLED && t_u + io.K <= p.T))) {
         const dim3 gr((unsigned)((p.cm.N + WAVE - 1) / WAVE));
@@ -1775,7 +1803,8 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
         // net_roll_kernel)
 #define RK_(RG)                                                                                                       \
     do {                                                                                                              \
-        if (pol) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
+        if (rnd) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG, true>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
+        else if (pol) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
         else if (p.cm.kn.net_roll3) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, false, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
         else hipLaunchKernelGGL((net_roll_kernel<G, RG>), gr, dim3(2 * WAVE), NetRoll<G>::lds(), s, p, t_u, io);    \
     } while (0)
@@ -1784,7 +1813,16 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
 #undef RK_
         return hipGetLastError();
     }
-    if (pol) {
+    if (pol && pol->kind == POL_RANDOM) {   // the RND variant of the policy instantiation
+#define KR_(TU)                                                                                            \
+    do {                                                                                                   \
+        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, true>), grid, block, lds, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, true>), grid, block, lds, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KR_(true);
+        else KR_(false);
+#undef KR_
+    } else if (pol) {
         if (t_u >= 0) K_(true, false, true);
         else K_(false, false, true);
     } else if (io.K == 1) {

@@ -377,7 +377,9 @@ __device__ __forceinline__ bool nv_step_regs(const NvParams &P, int64_t e, bool 
     return sc + 1 >= P.step_limit;                                          // :190
 }
 
-template <int LT, bool TU, bool ONE, bool POL, class G>
+// RND (POL_RANDOM, kernels.hpp ActGen): the order is drawn from the env's
+// action generator at the top of every launch step.
+template <int LT, bool TU, bool ONE, bool POL, class G, bool RND = false>
 __global__ void __launch_bounds__(WAVE)
 nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) float nv_tile[];
@@ -443,6 +445,8 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     const int K = ONE ? 1 : io.K;
     double lvl = 0.0;     // CLASSIC_NV / SS: the episode's ppf level, once computed
     bool have = false;
+    ActGen ag;
+    if constexpr (RND) ag.load(pol, S, el);
     // all lanes write the table: before any divergent step/reset branch (with a
     // lock-step single step there is none, and the write waits inside the step)
     if (!(ONE && TU)) ts.flush(lane);
@@ -451,6 +455,10 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
         float act;
         st.g.set_step(P.cm.ph_step + (uint64_t)k);
         if (!POL) act = io.act[(int64_t)k * N + el];
+        if constexpr (RND) {
+            act = act_draw(ag.g, pol.cf[0]);
+            if (valid && pol.act_out) out_store((float *)pol.act_out + oi, act);
+        }
         if (!(ONE && TU) && P.cm.autoreset == AR_NEXT_STEP && sc >= P.step_limit) {
             nv_reset_regs<LT>(P, e, st, trow, valid);
             have = false;
@@ -462,7 +470,7 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             sc = 0;
         } else {
             double r;
-            if (POL) {
+            if (POL && !RND) {
                 if (pol.kind == POL_ORDER_UP_TO) act = nv_order_up_to<LT>(P, pol, e, sc, st);
                 else if (pol.kind == POL_CLASSIC_NV) act = nv_classic<LT>(P, pol, e, sc, st, lvl, have);
                 else if (pol.kind == POL_SS) act = nv_ss<LT>(P, pol, e, sc, st, lvl, have);
@@ -504,6 +512,7 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
+        if constexpr (RND) ag.store(pol, S, e);
     }
     TWAIT();
     TPROBE(5);
@@ -1151,7 +1160,10 @@ __device__ __forceinline__ void nv_stream_ph(const NvParams &P, int role, int la
 #define NV_ROLL_WAVES 4
 #define NV_ROLL_BOUNDS __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(4)))   // <= 128 VGPRs: the grid resident
 
-template <int LT, bool POL, class RG = Pcg>
+// RND (POL_RANDOM, kernels.hpp ActGen): the dynamics wave draws each launch
+// step's order from the env's action generator, reset steps included; the
+// stream waves and their rings are as for the other agents.
+template <int LT, bool POL, class RG = Pcg, bool RND = false>
 __global__ void NV_ROLL_BOUNDS
 nv_roll_kernel(NvParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
     using R = NvRoll<LT>;
@@ -1450,6 +1462,8 @@ nv_roll_kernel(NvParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
     double lvl = 0.0;     // CLASSIC_NV / SS: the episode's ppf level, once computed
     bool have = false;
     int64_t dlast = -1;   // the last step's demand (the info record), -1: a reset step
+    ActGen ag;
+    if constexpr (RND) ag.load(pol, S, el);
     int kk = 0, cb = 0, c3 = 0;
     int ci = 0;
     (void)ci;
@@ -1459,6 +1473,10 @@ nv_roll_kernel(NvParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
         const int64_t oi = (int64_t)k * N + e;
         float act = nact;
         if (!POL && k + 1 < K) nact = io.act[(int64_t)(k + 1) * N + el];   // the next step's action
+        if constexpr (RND) {
+            act = act_draw(ag.g, pol.cf[0]);
+            if (valid && pol.act_out) out_store((float *)pol.act_out + oi, act);
+        }
         const bool rs = nxt && sc >= P.step_limit;
         if (rs) {                                                  // NEXT_STEP autoreset
             if (valid) {   // the ending episode's ring slots, as its per-step slot writes leave them
@@ -1481,7 +1499,7 @@ nv_roll_kernel(NvParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
             sc = 0;
             dlast = -1;
         } else {
-            if (POL) {
+            if (POL && !RND) {
                 if (pol.kind == POL_ORDER_UP_TO) act = nv_order_up_to<LT>(P, pol, e, sc, st);
                 else if (pol.kind == POL_CLASSIC_NV) act = nv_classic<LT>(P, pol, e, sc, st, lvl, have);
                 else if (pol.kind == POL_SS) act = nv_ss<LT>(P, pol, e, sc, st, lvl, have);
@@ -1528,6 +1546,7 @@ nv_roll_kernel(NvParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
+        if constexpr (RND) ag.store(pol, S, e);
     }
     TWAIT();
     TPROBE_W(6);
@@ -1628,6 +1647,7 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
         ahead = false;
         if (ce != hipSuccess) return ce;
     }
+    const bool rnd = pol && pol->kind == POL_RANDOM;
     if ((!pol || p.cm.kn.nv_pol_roll) && io.K > 1 && t_u >= 0 && p.L > 0 &&
         p.cm.autoreset != AR_SAME_STEP && p.cm.kn.nv_roll) {
         const dim3 gr(grid_for(p.cm.N, WAVE)), br(NV_ROLL_WAVES * WAVE);
@@ -1635,7 +1655,8 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
 #define R_(X)                                                                                              \
     do {                                                                                                   \
         if (X > 0) {                                                                                       \
-            if (pol) hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), true, RG>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
+            if (rnd) hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), true, RG, true>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
+            else if (pol) hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), true, RG>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
             else hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), false, RG>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
         } else done = false;                                                                               \
     } while (0)
@@ -1646,7 +1667,10 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
 #define K_(X, TU, ONE, POL) hipLaunchKernelGGL((nv_run_kernel<X, TU, ONE, POL, RG>), grid, block, lds, s, p, t_u, io, pv)
 #define L_(X)                                          \
     do {                                               \
-        if (pol) {                                     \
+        if (rnd) {                                     \
+            if (t_u >= 0) hipLaunchKernelGGL((nv_run_kernel<X, true, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);   \
+            else hipLaunchKernelGGL((nv_run_kernel<X, false, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);            \
+        } else if (pol) {                              \
             if (t_u >= 0) K_(X, true, false, true);    \
             else K_(X, false, false, true);            \
         } else if (io.K == 1) {                        \

@@ -26,6 +26,7 @@ _LAZY = {
     "OrderUpToHeuristicAgent": "policies",
     "ClassicNewsvendorAgent": "policies",
     "sSPolicyAgent": "policies",
+    "RandomAgent": "policies",
     "evaluate_agent": "policies",
     "rollout_policy": "policies",
     "StepGraph": "graphs",

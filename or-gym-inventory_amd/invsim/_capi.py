@@ -29,6 +29,7 @@ EXPORTS = (
     "invsim_debug_ptrs_stats", "invsim_set_demand_stream", "invsim_demand_stream",
     "invsim_capture_begin", "invsim_capture_end", "invsim_position",
     "invsim_episode_fold_groups", "invsim_set_episode_sink",
+    "invsim_action_rng_bytes", "invsim_seed_action_rng", "invsim_set_action_rng", "invsim_sample_actions",
 )
 ABI_VERSION = 4
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
@@ -62,7 +63,7 @@ class NetInvMgmtSpec(C.Structure):
         (n, C.c_void_p) for n in NET_TABLE_FIELDS]
 
 
-POLICY_KINDS = {"constant": 1, "base_stock": 2, "order_up_to": 3, "classic_nv": 4, "ss": 5}
+POLICY_KINDS = {"constant": 1, "base_stock": 2, "order_up_to": 3, "classic_nv": 4, "ss": 5, "random": 6}
 
 
 class PolicySpec(C.Structure):
@@ -114,6 +115,10 @@ def _declare(lib):
         "invsim_capture_begin": ([H], C.c_int),
         "invsim_capture_end": ([H, P], C.c_int),
         "invsim_position": ([H, P], C.c_int),
+        "invsim_action_rng_bytes": ([H, P], C.c_int),
+        "invsim_seed_action_rng": ([H, P, U64, U64, I64, P], C.c_int),
+        "invsim_set_action_rng": ([H, P], C.c_int),
+        "invsim_sample_actions": ([H, I32, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -17,6 +17,11 @@ Agents (restated from the reference, same names and constructor arguments):
   Newsvendor (scipy ``poisson.ppf`` restated on device, float32 loops included)
 * ``sSPolicyAgent(s_quantile, S_buffer_factor)`` benchmark_newsvendor_sb3_rllib.py:363-371,
   Newsvendor (the module's last definition; ``s_quantile`` is unused there too)
+* ``RandomAgent(seed)`` the ``RandomAgent`` every benchmark script's agent list
+  starts with (``env.action_space.sample()`` every step), any env and any graph.
+  The reference never seeds ``action_space``, so there is no trajectory to
+  match: the actions are numpy's ``Generator.uniform`` on a per-env PCG64
+  stream of their own (``include/invsim.h``, "RandomAgent")
 
 ``evaluate_agent(agent, env_cls, env_config, n_episodes, seed_offset)`` returns
 the reference's summary columns (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -24,7 +29,9 @@ benchmark_NetInvMgmtLostSalesEnv.py:241-312, benchmark_newsvendor.py:219-262):
 episode i is env i seeded ``seed_offset + i``.
 """
 import ctypes as C
+import os
 import time
+import weakref
 
 import numpy as np
 import torch
@@ -118,6 +125,51 @@ class sSPolicyAgent(_Agent):
         if env.family != _capi.INVSIM_NEWSVENDOR:
             raise TypeError("sSPolicyAgent needs a Newsvendor env")
         return _capi.PolicySpec(_capi.POLICY_KINDS["ss"], 0, float(self.S_buffer_factor), 0.0, None), None
+
+
+def _require_agreed_seed(seed, world):
+    """RandomAgent(seed=None) draws its base from OS entropy, which the ranks of
+    a distributed job would each draw differently: refuse before any collective."""
+    if seed is None and world > 1:
+        raise ValueError("RandomAgent(seed=None) under torch.distributed with more than one rank: every rank "
+                         "must use the same seed, pass one explicitly")
+
+
+class RandomAgent(_Agent):
+    """Uniform random actions over the env's action space, drawn in the step
+    kernel: env with global index g draws from
+    ``Generator(PCG64(SeedSequence(2**64 + seed + g)))``, ``action_dim`` doubles
+    per step (``uniform(0, high)`` for float32 spaces, ``floor(uniform(0, high +
+    1))`` for int64 ones).  The first time the agent meets an env it seeds the
+    env's action generators (``env.seed_actions(seed)``) and remembers that
+    buffer; later launches on that env continue it, so 5 steps then 7 equal 12.
+    If something else has attached other generators to the env since (another
+    agent, ``env.seed_actions``, ``env.set_action_rng_state``), the agent puts
+    its own buffer back first, so its stream on an env is always its own; to
+    continue from a restored checkpoint, sample with ``env.sample_actions``.
+    The first meeting launches the seeding kernel: under ``env.capture`` let
+    the agent meet the env (or call ``device_spec``) before the capture."""
+
+    name = "Random"
+
+    def __init__(self, seed=None):
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        _require_agreed_seed(seed, world)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little") >> 1      # 63 bits of OS entropy
+        self.seed = int(seed)
+        self._bufs = weakref.WeakKeyDictionary()       # env -> the generators this agent seeded for it
+
+    def device_spec(self, env):
+        buf = self._bufs.get(env)
+        if buf is None:
+            env.seed_actions(self.seed)
+            self._bufs[env] = env._arng
+        elif env._arng is not buf:
+            env._attach_action_rng(buf)
+        high = env._action_high()
+        return _capi.PolicySpec(_capi.POLICY_KINDS["random"], 0, 0.0, 0.0, high.ctypes.data), high
 
 
 def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metrics=None):

@@ -27,6 +27,9 @@ class _Box:
         return [seed]
 
     def sample(self):
+        """One host-side sample from this space's own numpy generator.  The
+        device-side random-action stream is ``invsim.RandomAgent`` /
+        ``env.sample_actions``, which does not draw from this generator."""
         if np.issubdtype(self.dtype, np.integer):
             return self.np_random.integers(self.low, self.high, endpoint=True).astype(self.dtype)
         return self.np_random.uniform(self.low, self.high).astype(self.dtype)

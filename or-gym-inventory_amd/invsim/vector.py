@@ -111,6 +111,7 @@ class InvSimVectorEnv:
             self._rec = torch.zeros((self.num_envs, d.value), dtype=rdt, device=self.device)
             _capi.check(self._lib.invsim_set_info_record(self._h, self._rec.data_ptr()), self._h, "set_info_record")
         self._out = None
+        self._arng = None     # RandomAgent's action generators (seed_actions)
 
     def _record_info(self, info):
         """Decode the per-step record into the reference's step-info names."""
@@ -279,6 +280,56 @@ class InvSimVectorEnv:
         invsim.policies); outputs optional, metrics [N, M] accumulated."""
         from .policies import rollout_policy
         return rollout_policy(self, agent, K, obs=obs, rewards=rewards, actions=actions, metrics=metrics)
+
+    # -- RandomAgent's action stream (include/invsim.h "RandomAgent") ----------
+    def _action_high(self):
+        """The action space's upper bounds in the action dtype (host array)."""
+        sp = self.single_action_space
+        return np.ascontiguousarray(np.asarray(sp.high, dtype=sp.dtype).reshape(-1))
+
+    def _attach_action_rng(self, buf):
+        _capi.check(self._lib.invsim_set_action_rng(self._h, buf.data_ptr() if buf is not None else None),
+                    self._h, "set_action_rng")
+        self._arng = buf
+
+    def seed_actions(self, seed):
+        """Allocate, seed and attach the per-env action generators: env i draws
+        its random actions from ``Generator(PCG64(SeedSequence(2**64 + seed +
+        global_offset + i)))``, a stream separate from the demand generator."""
+        seed = int(seed)
+        if seed < 0 or seed >= 2**64:
+            raise ValueError("action seed must be in [0, 2**64)")
+        b = _capi.C.c_int64()
+        _capi.check(self._lib.invsim_action_rng_bytes(self._h, _capi.C.byref(b)), self._h, "action_rng_bytes")
+        buf = torch.zeros((4, b.value // 32), dtype=torch.int64, device=self.device)
+        _capi.check(self._lib.invsim_seed_action_rng(self._h, buf.data_ptr(), seed, 1, self.global_offset,
+                                                     self._stream()), self._h, "seed_action_rng")
+        self._attach_action_rng(buf)
+
+    def sample_actions(self, K):
+        """K steps of random actions [K, N, A] (action dtype) from the attached
+        action generators, which advance as a RandomAgent rollout of K steps would."""
+        a = self._alloc(int(K), self.num_envs, self.action_dim, dtype=self.act_dtype)
+        high = self._action_high()
+        _capi.check(self._lib.invsim_sample_actions(self._h, int(K), high.ctypes.data, a.data_ptr(), self._stream()),
+                    self._h, "sample_actions")
+        return a
+
+    def action_rng_state(self):
+        """A clone of the action generators, int64 [4, Npad] (rows state hi / state
+        lo / inc hi / inc lo): the action stream's checkpoint."""
+        if getattr(self, "_arng", None) is None:
+            raise RuntimeError("no action generators: call seed_actions(seed) first")
+        return self._arng.clone()
+
+    def set_action_rng_state(self, t):
+        """Attach a copy of ``t`` (as returned by action_rng_state) as the action generators."""
+        t = torch.as_tensor(t, device=self.device)
+        b = _capi.C.c_int64()
+        _capi.check(self._lib.invsim_action_rng_bytes(self._h, _capi.C.byref(b)), self._h, "action_rng_bytes")
+        if t.dtype != torch.int64 or tuple(t.shape) != (4, b.value // 32):
+            raise ValueError(f"action generator state must be int64 [4, {b.value // 32}]")
+        self._attach_action_rng(t.contiguous().clone())
 
     def status(self, clear=True):
         """Sticky device status word (synchronous): bit 0 = an env was stepped past its
