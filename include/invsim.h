@@ -251,6 +251,32 @@ int invsim_metrics_dim(const invsim_handle *h, int32_t *dim);
 int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *policy, void *obs, double *reward,
                           uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream);
 
+/* K steps with caller-supplied actions, as invsim_rollout, that also keep
+ * evaluate_agent's per-env sums, as invsim_rollout_policy does for its agents:
+ * the entry point for policies that run outside the kernels (a torch network
+ * between K = 1 launches on the same stream, or open-loop [K][N][A] plans
+ * scored by their per-env return).
+ *   outputs    `actions` is required (INVSIM_EINVAL).  obs may be NULL; reward /
+ *              terminated / truncated are given together or not at all; metrics
+ *              may be NULL.
+ *   dynamics   identical to invsim_rollout with the same actions: where given,
+ *              obs, rewards and flags have the same bits, and so do the state
+ *              blob, info_demand and the info record afterwards.
+ *   metrics    accumulated exactly where and how invsim_rollout_policy
+ *              accumulates them: the same columns, += per applied step in step
+ *              order.  A NEXT_STEP reset step adds nothing; a step refused past
+ *              the horizon adds nothing.  A call with the actions an in-kernel
+ *              agent recorded leaves the metric bits of that agent's rollout.
+ *   shared     unavailable with SAME_STEP autoreset (INVSIM_EINVAL); the episode
+ *              sink (which then needs the reward triple), the capture bracket
+ *              and the horizon refusal (INVSIM_ERANGE, before any launch when
+ *              the period is lock-step) behave as for invsim_rollout_policy.
+ *              Both demand streams, every NetInvMgmt graph, per-env periods.
+ * Every K runs the one-wave run kernels (there is no fused variant). */
+int invsim_rollout_metrics(invsim_handle *h, int32_t K, const void *actions /* [K][N][A], action dtype */,
+                           void *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                           double *metrics /* [N][invsim_metrics_dim], += */, void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

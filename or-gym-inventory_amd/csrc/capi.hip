@@ -1153,6 +1153,25 @@ int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *poli
     return run_steps(h, K, nullptr, obs, reward, terminated, truncated, nullptr, (hipStream_t)stream, &p);
 }
 
+int invsim_rollout_metrics(invsim_handle *h, int32_t K, const void *actions, void *obs, double *reward,
+                           uint8_t *terminated, uint8_t *truncated, double *metrics, void *stream) {
+    TraceRange tr_("invsim_rollout_metrics");
+    if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
+    if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
+    if (K == 0) return INVSIM_OK;
+    if (h->cm.autoreset == AR_SAME_STEP)
+        return fail(h, INVSIM_EINVAL, "metric rollouts do not return final_obs: use NEXT_STEP or DISABLED autoreset");
+    if (h->N && !actions) return fail(h, INVSIM_EINVAL, "null actions");
+    if ((reward == nullptr) != (terminated == nullptr) || (reward == nullptr) != (truncated == nullptr))
+        return fail(h, INVSIM_EINVAL, "reward, terminated and truncated are given together or not at all");
+    PolicyIO p{};
+    p.kind = POL_EXTERNAL;   // the EXT run kernels: the policy bookkeeping, the actions of StepIO::act
+    p.metrics = metrics;
+    p.mdim = metrics_dim(h);
+    DeviceGuard g(h->device);
+    return run_steps(h, K, actions, obs, reward, terminated, truncated, nullptr, (hipStream_t)stream, &p);
+}
+
 int invsim_action_rng_bytes(const invsim_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(nullptr, INVSIM_EINVAL, "null argument");
     *bytes = 4 * h->Npad * (int64_t)sizeof(uint64_t);

@@ -41,6 +41,17 @@
 #define IM_RND_PARAM
 #define IM_RND_ARG
 #endif
+// invmgmt_ext.hip compiles this file with INVSIM_IM_EXT_TU: the policy
+// instantiations of im_run_kernel there are the EXTERNAL variant
+// (invsim_rollout_metrics): the policy bookkeeping (metrics, optional outputs)
+// with the caller's action rows (io.act), read as the open-loop path reads
+// them.  That translation unit defines im_ext_launch and emits im_run_kernel
+// only: the fused rollout kernels have no EXT variant.
+#ifdef INVSIM_IM_EXT_TU
+#define IM_EXT 1
+#else
+#define IM_EXT 0
+#endif
 
 namespace invsim {
 namespace {
@@ -539,6 +550,8 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
         int64_t pact[M1];
 #if IM_RND
         arow = ract;
+#elif IM_EXT
+        // the caller's row, as without a policy
 #else
         if (POL) {
             if (pol.kind == POL_BASE_STOCK) {
@@ -723,6 +736,10 @@ im_reset_kernel(ImParams P, const uint8_t *__restrict__ mask, int64_t *__restric
     }
 }
 
+// The EXT translation unit (invmgmt_ext.hip) holds im_run_kernel only: the
+// split step, the fused rollouts, the commit kernel and their launchers are
+// left out of it.
+#if !IM_EXT
 // Cross-wave LDS handoff inside a workgroup: orders LDS traffic only (an
 // __syncthreads() would also drain each wave's outstanding global loads and
 // stores, s_waitcnt vmcnt(0), before the s_barrier)
@@ -1974,9 +1991,11 @@ __global__ void __launch_bounds__(256) im_commit_kernel(ImParams P, int slot) {
     P.cm.rng.lo[e] = A[S + e];
     if (P.cm.u32buf) P.cm.u32buf[e] = A[3 * S + e];
 }
+#endif  // !IM_EXT
 
 inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
+#if !IM_EXT
 // the lock-step split step kernel applies (both streams)
 inline bool im_split_applies(const ImParams &p, int t_u, const PolicyIO *pol, const StepIO<int64_t, int64_t> &io) {
     return !pol && io.K == 1 && t_u >= 0 && t_u < p.periods && io.obs &&
@@ -2085,6 +2104,7 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
 }
 // the arguments of a launch, in the kernel's order (q: its ImParams, ha: the above)
 #define IM_SPLIT_ARGS io.act, q.I, q.B, q.Rring, q.alog32, ha.acur, ha.n32, ha.hw, q, t_u, io, cur, ha.apow, ha.n, ha.nw, ha.trunc
+#endif  // !IM_EXT
 
 #define IM_DISPATCH(M1V, BL, LAUNCH)                                  \
     switch (M1V) {                                                     \
@@ -2099,6 +2119,7 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
         default: return hipErrorInvalidValue;                          \
     }
 
+#if !IM_EXT
 // The split / rollout / run dispatch of one demand stream: RG = Pcg (numpy's
 // PCG64, parity) or PhiloxGen (the fast stream; instantiated in
 // invmgmt_ph.hip).  The parity stream's lookahead cache holds generator state,
@@ -2172,6 +2193,10 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
     // RANDOM: the same rows, from the RND translation unit (invmgmt_rnd.hip)
     if (pol && pol->kind == POL_RANDOM) return im_rnd_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
 #endif
+#if !IM_RND && !IM_EXT
+    // EXTERNAL: the caller's actions, the run kernel of invmgmt_ext.hip for any K
+    if (pol && pol->kind == POL_EXTERNAL) return im_ext_launch(p, M1, backlog, t_u, *pol, io, ph, s);
+#endif
     if (im_roll_applies(p, M1, t_u, pol, io)) {
         sunk = true;                  // so do the rollout kernels
         return im_roll_launch<RG>(p, backlog, t_u, pol, io, s);
@@ -2201,10 +2226,44 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
 #undef K_
     return hipGetLastError();
 }
+#endif  // !IM_EXT
 
 }  // namespace
 
-#if IM_RND
+#if IM_EXT
+// invmgmt_ext.hip: this file compiled a fourth time, for the EXTERNAL variant
+// of im_run_kernel's policy instantiations of both demand streams (one step or
+// K: invsim_rollout_metrics has no fused rollout).  The caller (im_launch_rg)
+// has committed the lookahead cache; the kernel does not fold into the episode
+// sink, so the host folds the output rows.
+template <class RG>
+static hipError_t im_ext_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                                   const StepIO<int64_t, int64_t> &io, hipStream_t s) {
+    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
+    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
+    const bool npd = p.dist >= 2 && p.dist <= 4;
+#define KE_(M, B, TU, NPD) hipLaunchKernelGGL((im_run_kernel<M, B, TU, false, true, NPD, RG>), grid, block, lds, s, p, t_u, io, pol)
+#define L_(M, B)                                \
+    do {                                        \
+        if (t_u >= 0) {                         \
+            if (npd) KE_(M, B, true, true);     \
+            else KE_(M, B, true, false);        \
+        } else {                                \
+            if (npd) KE_(M, B, false, true);    \
+            else KE_(M, B, false, false);       \
+        }                                       \
+    } while (0)
+    IM_DISPATCH(M1, backlog, L_)
+#undef L_
+#undef KE_
+    return hipGetLastError();
+}
+hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s) {
+    if (philox) return im_ext_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, s);
+    return im_ext_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, s);
+}
+#elif IM_RND
 // invmgmt_rnd.hip: this file compiled a third time, for the RANDOM variants of
 // the policy kernels of both demand streams: im_roll3o_kernel / im_roll3_kernel
 // where im_roll_applies (the rows of BaseStock / ConstantOrder),
@@ -2277,7 +2336,7 @@ INVSIM_PTRS_STATS_TU(im)
 
 }  // namespace invsim
 
-#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND
+#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND && !IM_EXT
 extern "C" int invsim_debug_timing(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbuf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }

@@ -392,8 +392,13 @@ struct StepIO {
 // Closed-loop rollouts (invsim_rollout_policy): each step's action is computed
 // in the kernel from the env state by a restated heuristic agent, every output
 // is optional, and per-env evaluation metrics accumulate in registers.
+// POL_EXTERNAL (invsim_rollout_metrics) is internal, not an INVSIM_POLICY_* kind:
+// the policy bookkeeping with the caller's action rows (StepIO::act).  It is a
+// compile-time variant, EXT, of the run kernels only (a trailing template
+// argument; for InvMgmt the translation unit invmgmt_ext.hip, INVSIM_IM_EXT_TU),
+// so no existing instantiation gains a branch.
 enum { POL_NONE = 0, POL_CONSTANT = 1, POL_BASE_STOCK = 2, POL_ORDER_UP_TO = 3, POL_CLASSIC_NV = 4,
-       POL_SS = 5, POL_RANDOM = 6 };
+       POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7 };
 constexpr int POL_MAX_A = 32;
 struct PolicyIO {
     int32_t kind;
@@ -677,6 +682,10 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
 // (the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
+// the EXTERNAL instantiations of im_run_kernel, invmgmt_ext.hip (both demand streams):
+// K >= 1 steps with the actions of io.act and the bookkeeping of pol (the rows are not sunk)
+hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s);
 // cm.rng <- the committed generator state held by the lookahead cache (whose
 // current slot is `slot`); needed before anything reads cm.rng while it is valid
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s);
@@ -688,7 +697,7 @@ hipError_t net_spec_launch(int which, const NetParams &p, int t_u, const PolicyI
                            const StepIO<float, float> &io, bool &ahead, int &slot, hipStream_t s);
 hipError_t net_commit_launch(const NetParams &p, int slot, hipStream_t s);
 hipError_t net_reset_launch(const NetParams &p, const uint8_t *mask, float *obs, hipStream_t s);
-// generic (table-walking) kernel; pol: CONSTANT policy rollouts, or null
+// generic (table-walking) kernel; pol: CONSTANT / RANDOM / EXTERNAL policy rollouts, or null
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
                           hipStream_t s);
 size_t net_lds_bytes(const NetParams &p);

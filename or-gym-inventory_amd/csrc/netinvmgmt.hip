@@ -217,7 +217,9 @@ __device__ bool net_step_lds(const NetParams &P, int64_t e, int gl, int t, RG &g
 // step are drawn from the env's action generator into the lane's row of an
 // LDS block behind the obs tile (net_act_lds_bytes), which the step reads as
 // its action row.
-template <bool TU, bool POL, class RG, bool RND = false>
+// EXT (POL_EXTERNAL, invsim_rollout_metrics): the policy bookkeeping with the
+// caller's action rows (io.act), as the open-loop path reads them.
+template <bool TU, bool POL, class RG, bool RND = false, bool EXT = false>
 __global__ void __launch_bounds__(WAVE)
 net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) double net_lds[];
@@ -280,7 +282,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             } else {
                 double r;
                 if (RG::kCounter) u32 = 0;          // fast stream: no half carried between steps
-                tr = net_step_lds(P, e, gl, t, g, u32, s, RND ? arow : POL ? pol.cf : io.act + oi * P.E, trow, r,
+                tr = net_step_lds(P, e, gl, t, g, u32, s, RND ? arow : (POL && !EXT) ? pol.cf : io.act + oi * P.E, trow, r,
                                   k == io.K - 1 ? P.cm.info_demand : nullptr,
                                   k == io.K - 1 ? (double *)P.cm.info_rec : nullptr);
                 if (leader && (!POL || io.rew)) {
@@ -289,7 +291,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
                     io.trunc[oi] = tr ? 1 : 0;
                 }
                 if (POL && leader) {
-                    if (!RND && pol.act_out)
+                    if (!RND && !EXT && pol.act_out)
                         for (int q = 0; q < P.E; q++) ((float *)pol.act_out)[oi * P.E + q] = pol.cf[q];
                     if (pol.metrics) {   // evaluate_agent metrics (benchmark_NetInvMgmtLostSalesEnv.py:264-300)
                         double *met = pol.metrics + e * (5 + P.J);
@@ -375,7 +377,19 @@ hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, cons
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
     PolicyIO none{};
     const PolicyIO &pv = pol ? *pol : none;
-    if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM) return hipErrorInvalidValue;
+    if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM && pol->kind != POL_EXTERNAL)
+        return hipErrorInvalidValue;
+    if (pol && pol->kind == POL_EXTERNAL) {
+#define KE_(TU)                                                                                        \
+    do {                                                                                               \
+        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, false, true>), grid, block, lds, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KE_(true);
+        else KE_(false);
+#undef KE_
+        return hipGetLastError();
+    }
     if (pol && pol->kind == POL_RANDOM) {
         const size_t ldr = net_random_lds_bytes(p);
         if (ldr > 160 * 1024) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first, INVSIM_ERANGE)

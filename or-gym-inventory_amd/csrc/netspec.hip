@@ -298,7 +298,9 @@ __device__ __forceinline__ void spec_shift(NetSt<G, RG> &s, const double (&Rn)[G
 
 // RND (POL_RANDOM, kernels.hpp ActGen): the reorder quantities are drawn from
 // the env's action generator at the top of every launch step.
-template <class G, bool TU, bool ONE, bool POL, class RG, bool RND = false>
+// EXT (POL_EXTERNAL, invsim_rollout_metrics): the policy bookkeeping with the
+// caller's action rows (io.act), read as the open-loop path reads them.
+template <class G, bool TU, bool ONE, bool POL, class RG, bool RND = false, bool EXT = false>
 __global__ void __launch_bounds__(WAVE)
 net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) float ns_lds[];
@@ -371,7 +373,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     }
     float act[G::E];
 #pragma unroll
-    for (int k = 0; k < G::E; k++) act[k] = POL ? pol.cf[k] : io.act[el * G::E + k];
+    for (int k = 0; k < G::E; k++) act[k] = (POL && !EXT) ? pol.cf[k] : io.act[el * G::E + k];
     constexpr int MD = 5 + G::J;             // metrics: reward, steps, demand, sales, stockout, X per node
     double met[MD];
 #pragma unroll
@@ -396,7 +398,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
         st.g.set_step(P.cm.ph_step + (uint64_t)kk);
         if (kk > 0) {
             const int64_t ea = (int64_t)kk * N + el;
-            if (!POL) {
+            if (!POL || EXT) {
 #pragma unroll
                 for (int k = 0; k < G::E; k++) act[k] = io.act[ea * G::E + k];
             }
@@ -433,7 +435,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             if (POL) {
                 met[0] += r;                    // episode_reward += reward
                 met[1] += 1.0;
-                if (!RND && valid && pol.act_out) {
+                if (!RND && !EXT && valid && pol.act_out) {
 #pragma unroll
                     for (int k = 0; k < G::E; k++) out_store((float *)pol.act_out + oi * G::E + k, act[k]);
                 }
@@ -1822,6 +1824,15 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
         if (t_u >= 0) KR_(true);
         else KR_(false);
 #undef KR_
+    } else if (pol && pol->kind == POL_EXTERNAL) {   // the EXT variant: the caller's actions, K >= 1
+#define KE_(TU)                                                                                            \
+    do {                                                                                                   \
+        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, false, true>), grid, block, lds, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KE_(true);
+        else KE_(false);
+#undef KE_
     } else if (pol) {
         if (t_u >= 0) K_(true, false, true);
         else K_(false, false, true);

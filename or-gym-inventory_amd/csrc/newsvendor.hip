@@ -379,7 +379,9 @@ __device__ __forceinline__ bool nv_step_regs(const NvParams &P, int64_t e, bool 
 
 // RND (POL_RANDOM, kernels.hpp ActGen): the order is drawn from the env's
 // action generator at the top of every launch step.
-template <int LT, bool TU, bool ONE, bool POL, class G, bool RND = false>
+// EXT (POL_EXTERNAL, invsim_rollout_metrics): the policy bookkeeping with the
+// caller's orders (io.act), read as the open-loop path reads them.
+template <int LT, bool TU, bool ONE, bool POL, class G, bool RND = false, bool EXT = false>
 __global__ void __launch_bounds__(WAVE)
 nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) float nv_tile[];
@@ -454,7 +456,7 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
         const int64_t oi = (int64_t)k * N + e;
         float act;
         st.g.set_step(P.cm.ph_step + (uint64_t)k);
-        if (!POL) act = io.act[(int64_t)k * N + el];
+        if (!POL || EXT) act = io.act[(int64_t)k * N + el];
         if constexpr (RND) {
             act = act_draw(ag.g, pol.cf[0]);
             if (valid && pol.act_out) out_store((float *)pol.act_out + oi, act);
@@ -470,7 +472,7 @@ nv_run_kernel(NvParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             sc = 0;
         } else {
             double r;
-            if (POL && !RND) {
+            if (POL && !RND && !EXT) {
                 if (pol.kind == POL_ORDER_UP_TO) act = nv_order_up_to<LT>(P, pol, e, sc, st);
                 else if (pol.kind == POL_CLASSIC_NV) act = nv_classic<LT>(P, pol, e, sc, st, lvl, have);
                 else if (pol.kind == POL_SS) act = nv_ss<LT>(P, pol, e, sc, st, lvl, have);
@@ -1648,7 +1650,8 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
         if (ce != hipSuccess) return ce;
     }
     const bool rnd = pol && pol->kind == POL_RANDOM;
-    if ((!pol || p.cm.kn.nv_pol_roll) && io.K > 1 && t_u >= 0 && p.L > 0 &&
+    const bool ext = pol && pol->kind == POL_EXTERNAL;   // the run kernel only: there is no fused EXT rollout
+    if ((!pol || (p.cm.kn.nv_pol_roll && !ext)) && io.K > 1 && t_u >= 0 && p.L > 0 &&
         p.cm.autoreset != AR_SAME_STEP && p.cm.kn.nv_roll) {
         const dim3 gr(grid_for(p.cm.N, WAVE)), br(NV_ROLL_WAVES * WAVE);
         bool done = true;
@@ -1670,6 +1673,9 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
         if (rnd) {                                     \
             if (t_u >= 0) hipLaunchKernelGGL((nv_run_kernel<X, true, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);   \
             else hipLaunchKernelGGL((nv_run_kernel<X, false, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);            \
+        } else if (ext) {                              \
+            if (t_u >= 0) hipLaunchKernelGGL((nv_run_kernel<X, true, false, true, RG, false, true>), grid, block, lds, s, p, t_u, io, pv);  \
+            else hipLaunchKernelGGL((nv_run_kernel<X, false, false, true, RG, false, true>), grid, block, lds, s, p, t_u, io, pv);           \
         } else if (pol) {                              \
             if (t_u >= 0) K_(X, true, false, true);    \
             else K_(X, false, false, true);            \

@@ -27,6 +27,8 @@ _LAZY = {
     "ClassicNewsvendorAgent": "policies",
     "sSPolicyAgent": "policies",
     "RandomAgent": "policies",
+    "TorchPolicyAgent": "policies",
+    "convert_actions": "policies",
     "evaluate_agent": "policies",
     "rollout_policy": "policies",
     "StepGraph": "graphs",

@@ -30,6 +30,7 @@ EXPORTS = (
     "invsim_capture_begin", "invsim_capture_end", "invsim_position",
     "invsim_episode_fold_groups", "invsim_set_episode_sink",
     "invsim_action_rng_bytes", "invsim_seed_action_rng", "invsim_set_action_rng", "invsim_sample_actions",
+    "invsim_rollout_metrics",
 )
 ABI_VERSION = 4
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
@@ -101,6 +102,7 @@ def _declare(lib):
         "invsim_info_record_dim": ([H, P], C.c_int),
         "invsim_set_info_record": ([H, P], C.c_int),
         "invsim_rollout_policy": ([H, I32, P, P, P, P, P, P, P, P], C.c_int),
+        "invsim_rollout_metrics": ([H, I32, P, P, P, P, P, P, P], C.c_int),
         "invsim_set_info_demand": ([H, P], C.c_int),
         "invsim_state_bytes": ([H, P], C.c_int),
         "invsim_state_field": ([H, I32, P, P, P, P, P], C.c_int),

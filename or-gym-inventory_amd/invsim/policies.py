@@ -23,6 +23,14 @@ Agents (restated from the reference, same names and constructor arguments):
   match: the actions are numpy's ``Generator.uniform`` on a per-env PCG64
   stream of their own (``include/invsim.h``, "RandomAgent")
 
+Policies computed outside the kernels (a trained ``torch.nn.Module`` actor, the
+scripts' ``SB3AgentWrapper``: benchmark_InvManagementBacklogEnv.py:332-342) go
+through ``TorchPolicyAgent(fn)``: the network runs in torch on the env's device
+and stream between one-step ``invsim_rollout_metrics`` launches, which keep the
+same per-env sums for the actions they are handed, so ``rollout_policy`` and
+``evaluate_agent`` take the agent like any other; ``convert_actions`` is the
+wrapper's post-processing of the network's output.
+
 ``evaluate_agent(agent, env_cls, env_config, n_episodes, seed_offset)`` returns
 the reference's summary columns (benchmark_InvManagementBacklogEnv.py:346-440,
 benchmark_NetInvMgmtLostSalesEnv.py:241-312, benchmark_newsvendor.py:219-262):
@@ -172,10 +180,115 @@ class RandomAgent(_Agent):
         return _capi.PolicySpec(_capi.POLICY_KINDS["random"], 0, 0.0, 0.0, high.ctypes.data), high
 
 
-def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metrics=None):
-    """K steps of every env of ``env`` under ``agent`` (in-kernel).  Returns a
-    dict with the requested device tensors; ``metrics`` (float64 [N, M]) is
-    accumulated in place when given."""
+def convert_actions(raw, low, high, dtype):
+    """What the reference's ``SB3AgentWrapper.get_action`` does to a network's
+    output, on torch tensors: ``np.clip(raw, low, high)`` (SB3 ``predict`` clips
+    the actions of unsquashed policies to the Box bounds; an infinite bound
+    leaves the value alone) and then ``.astype(action_space.dtype)``, which for
+    int64 spaces truncates toward zero.  ``raw`` [..., A] float tensor;
+    ``low`` / ``high`` [A] (tensors or arrays, the space's bounds); ``dtype``
+    torch.int64 or torch.float32.
+
+    NaN: numpy leaves ``nan.astype(int64)`` undefined, so for int64 spaces a NaN
+    maps to 0 (no order); for float spaces a NaN passes through unchanged, as
+    ``np.clip`` passes it, and the env's dynamics see it.  Signed zero: a -0.0
+    clipped at a bound of 0 gives +0.0, the bound."""
+    lo = torch.as_tensor(low, device=raw.device)
+    hi = torch.as_tensor(high, device=raw.device)
+    if dtype == torch.int64:
+        # numpy promotes float32 values with int64 bounds to float64: clip there
+        x = torch.clamp(raw.to(torch.float64), lo.to(torch.float64), hi.to(torch.float64))
+        x = torch.where(x != x, torch.zeros_like(x), x)
+        return x.to(torch.int64)                    # truncation toward zero
+    # promotes as np.clip does; NaN and a value at an infinite bound pass.  A value
+    # equal to a bound becomes the bound, so -0.0 at a bound of 0 is +0.0 (numpy's
+    # own result for that one input depends on the code path it takes)
+    nan = raw != raw
+    x = torch.where((raw > lo) | nan, raw, lo)
+    return torch.where((x < hi) | nan, x, hi).to(dtype)
+
+
+class TorchPolicyAgent(_Agent):
+    """A policy computed in torch, outside the kernels: ``fn`` is any callable
+    (an ``nn.Module`` actor, a lambda around one) on the env's device.  Every
+    step it receives the observations as float32 ``[N, O]`` (the scripts'
+    ``observation.astype(np.float32)``) and returns raw actions ``[N, A]``,
+    which ``convert_actions`` clips to the action space and casts to its dtype
+    (``clip=False``: cast only; the caller answers for the range).  It runs
+    under ``torch.no_grad()`` on the env's current stream, so a rollout is one
+    stream of launches with no host round trip.
+
+    A squashed (tanh) actor, SAC's, is unscaled by the caller in ``fn``:
+    ``lambda o: low + 0.5 * (actor(o) + 1.0) * (high - low)``."""
+
+    def __init__(self, fn, name="TorchPolicy", clip=True):
+        if not callable(fn):
+            raise TypeError("TorchPolicyAgent needs a callable (obs [N, O] float32 -> actions [N, A])")
+        self.fn = fn
+        self.name = name
+        self.clip = bool(clip)
+
+    def device_spec(self, env):
+        raise TypeError("TorchPolicyAgent runs outside the kernels: use rollout_policy / evaluate_agent")
+
+
+def _rollout_torch(env, agent, K, obs, rewards, actions, metrics, obs0):
+    """The closed loop of a TorchPolicyAgent: fn -> convert_actions -> one
+    invsim_rollout_metrics step, K times on the env's stream, every step
+    writing row k of the preallocated outputs."""
+    if obs0 is None:
+        raise ValueError("a TorchPolicyAgent rollout needs obs0, the observation the env last returned "
+                         "(reset()'s, or the last row of the previous rollout's obs)")
+    N, dev, A = env.num_envs, env.device, env.action_dim
+    obs0 = torch.as_tensor(obs0, device=dev)
+    if tuple(obs0.shape) != (N, env.obs_dim):
+        raise ValueError(f"obs0 must have shape {(N, env.obs_dim)}, got {tuple(obs0.shape)}")
+    metrics = env._metrics_arg(metrics)
+    sp = env.single_action_space
+    low = torch.as_tensor(np.asarray(sp.low).reshape(-1), device=dev)
+    high = torch.as_tensor(np.asarray(sp.high).reshape(-1), device=dev)
+    out = {}
+    # without obs the loop keeps only the last row: fn has read it (stream order) when the step overwrites it
+    o = torch.empty((K if obs else 1, N, env.obs_dim), dtype=env.obs_dtype, device=dev)
+    if rewards:
+        out["reward"] = torch.empty((K, N), dtype=torch.float64, device=dev)
+        out["terminated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+        out["truncated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+    a_all = torch.empty((K, N, A), dtype=env.act_dtype, device=dev) if actions else None
+    rew, term, trunc = out.get("reward"), out.get("terminated"), out.get("truncated")
+    cur = obs0
+    with torch.no_grad():
+        for k in range(K):
+            raw = agent.fn(cur.to(torch.float32))
+            a = convert_actions(raw, low, high, env.act_dtype) if agent.clip else raw.to(env.act_dtype)
+            if a.numel() != N * A:
+                raise ValueError(f"the policy must return actions of shape {(N, A)}, got {tuple(raw.shape)}")
+            a = a.reshape(N, A)
+            if a_all is not None:
+                a_all[k].copy_(a)
+                a = a_all[k]
+            elif not a.is_contiguous():
+                a = a.contiguous()
+            ok = o[k if obs else 0]
+            env._rollout_metrics(1, a, ok, rew[k] if rewards else None, term[k] if rewards else None,
+                                 trunc[k] if rewards else None, metrics)
+            cur = ok
+    if obs:
+        out["obs"] = o
+    if actions:
+        out["actions"] = a_all
+    return out
+
+
+def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metrics=None, obs0=None):
+    """K steps of every env of ``env`` under ``agent``.  Returns a dict with
+    the requested device tensors; ``metrics`` (float64 [N, M]) is accumulated in
+    place when given.  The heuristic agents run in the step kernel, one launch;
+    a ``TorchPolicyAgent`` runs in torch between K one-step launches and needs
+    ``obs0``, the observation the env last returned (``actions`` then records
+    what the policy produced at every step, reset steps included)."""
+    if isinstance(agent, TorchPolicyAgent):
+        return _rollout_torch(env, agent, int(K), obs, rewards, actions, metrics, obs0)
     spec, keep = agent.device_spec(env)
     N, dev = env.num_envs, env.device
     out = {}
@@ -244,7 +357,8 @@ def _gather_rows(met, n_episodes, world, rank, group):
 
 def evaluate_agent(agent, env_cls, env_config=None, n_episodes=100, seed_offset=0, device=None, group=None):
     """Batched evaluate_agent: episode i = env i seeded seed_offset + i, one
-    full episode under ``agent`` in one kernel launch.  Returns a dict of
+    full episode under ``agent`` in one kernel launch (a ``TorchPolicyAgent``:
+    one launch per step, with the policy's torch ops between).  Returns a dict of
     per-episode columns (the reference's summary DataFrame columns).
 
     Under torch.distributed (one process per GPU) the episodes are sharded by
@@ -261,12 +375,12 @@ def evaluate_agent(agent, env_cls, env_config=None, n_episodes=100, seed_offset=
     env = env_cls(num_envs=max(n_loc, 1), device=device, autoreset_mode="disabled", global_offset=off,
                   **(env_config or {}))
     try:
-        env.reset(seed=seed_offset)
+        obs0, _ = env.reset(seed=seed_offset)
         M = metrics_dim(env)
         met = torch.zeros((env.num_envs, M), dtype=torch.float64, device=env.device)
         torch.cuda.synchronize(env.device)
         t0 = time.perf_counter()
-        rollout_policy(env, agent, env._horizon(), obs=False, rewards=False, metrics=met)
+        rollout_policy(env, agent, env._horizon(), obs=False, rewards=False, metrics=met, obs0=obs0)
         torch.cuda.synchronize(env.device)
         dt = time.perf_counter() - t0
         met = met[:n_loc]

@@ -275,11 +275,56 @@ class InvSimVectorEnv:
                     self._h, "rollout")
         return obs, rew, term, trunc
 
-    def rollout_policy(self, agent, K, obs=False, rewards=True, actions=False, metrics=None):
-        """K steps with the agent's actions computed in the kernel (see
-        invsim.policies); outputs optional, metrics [N, M] accumulated."""
+    def rollout_policy(self, agent, K, obs=False, rewards=True, actions=False, metrics=None, obs0=None):
+        """K steps with the agent's actions computed in the kernel, or in torch
+        for a TorchPolicyAgent (which needs obs0; see invsim.policies);
+        outputs optional, metrics [N, M] accumulated."""
         from .policies import rollout_policy
-        return rollout_policy(self, agent, K, obs=obs, rewards=rewards, actions=actions, metrics=metrics)
+        return rollout_policy(self, agent, K, obs=obs, rewards=rewards, actions=actions, metrics=metrics,
+                              obs0=obs0)
+
+    def _rollout_metrics(self, K, a, obs, rew, term, trunc, metrics):
+        """invsim_rollout_metrics on tensors in the kernel's layout (any output may be None)."""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _capi.check(self._lib.invsim_rollout_metrics(self._h, int(K), a.data_ptr(), p(obs), p(rew), p(term),
+                                                     p(trunc), p(metrics), self._stream()),
+                    self._h, "rollout_metrics")
+
+    def _metrics_arg(self, metrics):
+        if metrics is None:
+            return None
+        if getattr(self, "_mdim", None) is None:
+            d = _capi.C.c_int32()
+            _capi.check(self._lib.invsim_metrics_dim(self._h, _capi.C.byref(d)), self._h, "metrics_dim")
+            self._mdim = d.value
+        if (type(metrics) is not torch.Tensor or metrics.dtype != torch.float64 or metrics.device != self.device
+                or not metrics.is_contiguous() or tuple(metrics.shape) != (self.num_envs, self._mdim)):
+            raise ValueError(f"metrics must be a contiguous float64 tensor [{self.num_envs}, {self._mdim}] on {self.device}")
+        return metrics
+
+    def rollout_metrics(self, actions, metrics=None, obs=True, rewards=True):
+        """K consecutive steps with the caller's actions [K, N, A], as
+        rollout(), that also add evaluate_agent's per-env sums to ``metrics``
+        (float64 [N, M], in place), as rollout_policy() does for its in-kernel
+        agents: the entry point for policies computed outside the kernels and
+        for scoring open-loop action plans.  Returns a dict with the requested
+        device tensors: "obs" [K, N, O]; "reward", "terminated", "truncated"
+        [K, N].  next_step / disabled autoreset."""
+        a = torch.as_tensor(actions)
+        K = int(a.shape[0])
+        a = self._actions(a, (K, self.num_envs))
+        metrics = self._metrics_arg(metrics)
+        N = self.num_envs
+        out = {}
+        o = self._alloc(K, N, self.obs_dim, dtype=self.obs_dtype) if obs else None
+        if rewards:
+            out["reward"] = self._alloc(K, N, dtype=torch.float64)
+            out["terminated"] = self._alloc(K, N, dtype=torch.bool)
+            out["truncated"] = self._alloc(K, N, dtype=torch.bool)
+        self._rollout_metrics(K, a, o, out.get("reward"), out.get("terminated"), out.get("truncated"), metrics)
+        if obs:
+            out["obs"] = o
+        return out
 
     # -- RandomAgent's action stream (include/invsim.h "RandomAgent") ----------
     def _action_high(self):
