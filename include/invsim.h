@@ -277,6 +277,106 @@ int invsim_rollout_metrics(invsim_handle *h, int32_t K, const void *actions /* [
                            void *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
                            double *metrics /* [N][invsim_metrics_dim], += */, void *stream);
 
+/* ---- MLP actor: a trained feed-forward policy evaluated by the library, one
+ * kernel per step (the actors the reference's scripts wrap in SB3AgentWrapper,
+ * benchmark_InvManagementBacklogEnv.py:332-342; SB3's mlp_extractor +
+ * action_net).  The network is a kernel of its own, observations in, actions
+ * out; invsim_rollout_mlp issues the closed loop in C: per step that kernel and
+ * then the one-step run kernel of invsim_rollout_metrics, on one stream, with
+ * no host round trip.
+ *
+ * Arithmetic contract.  Results here are defined bit for bit, so the network is
+ * defined op by op; a CPU restatement reproduces it exactly.
+ *   numbers    everything is IEEE binary32, round to nearest, subnormals kept.
+ *              Every multiply-add is one fused fmaf(a, b, c) (one rounding);
+ *              there is no unfused a * b + c anywhere.
+ *   input      x[i] = (float)obs[i]: int64 observations are cast round to
+ *              nearest (numpy's astype(float32)), f32 ones are taken as they
+ *              are.  With in_scale: x[i] = fmaf(x[i], in_scale[i], in_shift[i]).
+ *   linear     layer l, output unit j: acc = bias[l][j] (+0.0f without a bias);
+ *              then for i = 0 .. in - 1 in ascending order
+ *              acc = fmaf(W[l][j][i], x[i], acc).  The order within one unit is
+ *              the contract; how units are spread over lanes and waves is not.
+ *   hidden     one activation kind per network, after every layer but the last:
+ *              INVSIM_MLP_RELU  acc > 0 ? acc : +0.0f (a NaN gives +0.0f);
+ *              INVSIM_MLP_TANH  the device's tanhf(acc).
+ *   output     out_activation NONE or TANH on the last layer's units; then, with
+ *              out_scale, raw[a] = fmaf(raw[a], out_scale[a], out_shift[a]) (the
+ *              rescaling of a squashed actor: low + 0.5 (tanh + 1) (high - low)
+ *              is out_scale = 0.5 (high - low), out_shift = low + out_scale).
+ *   conversion raw -> action is invsim.policies.convert_actions.  int64 spaces:
+ *              promote to f64; with clip, x < low ? low : x, then x > high ?
+ *              high : x, on the bounds as f64; NaN -> 0; truncate toward zero
+ *              (without clip the caller answers for the int64 range).  f32
+ *              spaces: with clip, (r > low || r is NaN) ? r : low, then (x < high
+ *              || NaN) ? x : high: a NaN passes, an infinite bound leaves the
+ *              value alone, a value equal to a bound becomes the bound (-0.0 at
+ *              a bound of 0 gives +0.0).
+ * A RELU or purely linear network without a TANH output activation is therefore
+ * reproducible bit for bit on a CPU.  TANH networks are defined up to the
+ * device's tanhf: its last-ulp results are the ROCm device library's, not
+ * glibc's; everything around it is still exact (actions == the conversion of
+ * the raw outputs the kernel reports).  No matrix-core instructions are used:
+ * their accumulation order could not be restated.
+ *
+ * invsim_mlp_create validates on the host before any device call: n_layers
+ * outside 1..INVSIM_MLP_MAX_LAYERS, dims[0] != obs_dim, dims[n_layers] !=
+ * action_dim, a hidden width outside 1..INVSIM_MLP_MAX_WIDTH, obs_dim >
+ * INVSIM_MLP_MAX_WIDTH or action_dim > INVSIM_POLICY_MAX_ACTION return
+ * INVSIM_ERANGE; unknown activation kinds, a scale without its shift, clip
+ * without bounds and null arguments return INVSIM_EINVAL.  It copies the
+ * parameters to the handle's GPU, allocates the closed loop's scratch (one
+ * [N][O] obs row, one [N][A] action row), and may synchronise: not during
+ * capture.  The object belongs to the handle it was created for (another
+ * handle: INVSIM_EINVAL) and must be destroyed before it.  invsim_mlp_destroy
+ * frees device memory, which synchronises: inside a capture bracket it does
+ * nothing but set the handle's error message, and the object stays valid.
+ *
+ * invsim_mlp_actions is one launch, obs rows -> raw outputs and / or actions;
+ * it does not touch env state and is legal inside a capture bracket.
+ *
+ * invsim_rollout_mlp: for k = 0 .. K - 1 the network reads obs0 (k = 0) or obs
+ * row k - 1 and one env step with those actions writes obs row k.  obs0 is
+ * required (INVSIM_EINVAL); when `obs` is given its rows are both the output
+ * and the next step's input, otherwise (and for `actions`) the object's
+ * scratch rows are used.  In everything else it is invsim_rollout_metrics
+ * with the actions the network produced: SAME_STEP refused, the reward triple
+ * together or not at all, metrics += per applied step (a NEXT_STEP reset step
+ * still runs the network and records its action, and adds nothing), episode
+ * sink (the call's K output rows are folded once, after the loop, as
+ * invsim_episode_fold_groups over those K rows would), capture bracket, both
+ * demand streams, every NetInvMgmt graph, per-env periods.  The lock-step horizon refusal (INVSIM_ERANGE) covers all K steps
+ * and comes before the first launch; with per-env periods and DISABLED
+ * autoreset the status word is read once, after the loop. */
+#define INVSIM_MLP_NONE 0
+#define INVSIM_MLP_RELU 1
+#define INVSIM_MLP_TANH 2
+#define INVSIM_MLP_MAX_LAYERS 5     /* linear layers: up to 4 hidden */
+#define INVSIM_MLP_MAX_WIDTH 256    /* hidden units per layer */
+
+typedef struct {
+    int32_t n_layers;               /* linear layers, 1..INVSIM_MLP_MAX_LAYERS */
+    int32_t activation;             /* hidden: RELU or TANH (ignored when n_layers == 1) */
+    int32_t out_activation;         /* NONE or TANH */
+    int32_t clip;                   /* 1: clamp to the bounds below */
+    const int32_t *dims;            /* host [n_layers + 1]; dims[0] = obs_dim, dims[n_layers] = action_dim */
+    const float *const *weight;     /* host [n_layers] -> row-major [dims[l+1]][dims[l]] (torch Linear.weight) */
+    const float *const *bias;       /* host [n_layers] -> [dims[l+1]]; the array or an entry may be NULL */
+    const float *in_scale, *in_shift;    /* host [obs_dim], both or neither */
+    const float *out_scale, *out_shift;  /* host [action_dim], both or neither */
+    const void *low, *high;         /* host [action_dim], action dtype; needed when clip */
+} invsim_mlp_spec;
+typedef struct invsim_mlp invsim_mlp;
+
+int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *spec, invsim_mlp **out);
+void invsim_mlp_destroy(invsim_mlp *m);
+int invsim_mlp_actions(invsim_handle *h, const invsim_mlp *m, const void *obs /* [N][O], obs dtype */,
+                       void *actions /* [N][A], action dtype, may be NULL */,
+                       float *raw /* [N][A], may be NULL */, void *stream);
+int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0 /* [N][O] */,
+                       void *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                       void *actions, double *metrics, void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

@@ -13,6 +13,7 @@
 
 #include "../../include/invsim.h"
 #include "kernels.hpp"
+#include "mlp_policy.hpp"
 
 using namespace invsim;
 
@@ -86,6 +87,17 @@ struct invsim_handle {
     std::string err;
 };
 
+// An MLP actor of one handle (invsim_mlp_create): the kernel's argument block,
+// the device blob it points into, and the closed loop's scratch rows.
+struct invsim_mlp {
+    invsim_handle *owner = nullptr;
+    MlpDev dev{};               // host copy (launch geometry); the kernel reads dev_copy
+    const MlpDev *dev_copy = nullptr;
+    float *blob = nullptr;
+    void *obs_row = nullptr;    // [N][O], obs dtype
+    void *act_row = nullptr;    // [N][A], action dtype
+};
+
 namespace {
 
 // roctx range around an ABI call (SURVEY §5 tracing: step / rollout / reset
@@ -136,6 +148,13 @@ int fail(invsim_handle *h, int code, const std::string &msg) {
     if (h) h->err = msg;
     g_last_error = msg;
     return code;
+}
+
+void mlp_free(invsim_mlp *m) {
+    if (m->blob) (void)hipFree(m->blob);
+    if (m->obs_row) (void)hipFree(m->obs_row);
+    if (m->act_row) (void)hipFree(m->act_row);
+    delete m;
 }
 
 int hip_fail(invsim_handle *h, hipError_t e, const char *what) {
@@ -952,9 +971,11 @@ int invsim_reset(invsim_handle *h, const uint8_t *mask, void *obs, void *stream)
     return INVSIM_OK;
 }
 
-static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, double *reward,
-                     uint8_t *terminated, uint8_t *truncated, void *final_obs, hipStream_t s,
-                     const PolicyIO *pol = nullptr) {
+// A call that steps every env K times is steps_begin (every refusal that needs
+// no device work, for all K steps, before the first launch), one or more
+// steps_launch whose step counts add up to K, and steps_end.  run_steps is the
+// three in a row; invsim_rollout_mlp puts K one-step launches between them.
+static int steps_begin(invsim_handle *h, int K, const double *reward, hipStream_t s) {
     if (int rc = capture_check(h, s)) return rc;
     if (h->capturing) {
         if (h->demand_stream == INVSIM_DEMAND_PHILOX)
@@ -965,9 +986,7 @@ static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, do
                                           "the horizon check reads the device status word (a host synchronisation)");
         h->cap_steps += K;
     }
-    int t_u = -1;
     if (h->t_known) {
-        t_u = h->t_cur;
         // DISABLED autoreset: refuse to step InvMgmt/NetInvMgmt past the horizon
         // (the reference raises IndexError, inventory_management.py:267)
         int t = h->t_cur;
@@ -977,14 +996,20 @@ static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, do
             t = next_period(t, h->horizon, h->cm.autoreset, h->past_ok);
         }
     }
+    // episode sink: a kernel that does not fold in-kernel leaves it to the
+    // group fold of its output rows (the same arithmetic, kernels.hpp EpSink)
+    if (h->cm.ep_ret && h->N && !reward)
+        return fail(h, INVSIM_EINVAL, "the episode sink folds the reward outputs: pass reward / terminated / truncated");
+    return INVSIM_OK;
+}
+
+static int steps_launch(invsim_handle *h, int K, const void *actions, void *obs, double *reward,
+                        uint8_t *terminated, uint8_t *truncated, void *final_obs, hipStream_t s, const PolicyIO *pol) {
+    const int t_u = h->t_known ? h->t_cur : -1;
     if (h->demand_stream == INVSIM_DEMAND_PHILOX) {
         int rc = ph_counter_sync(h, s);
         if (rc != INVSIM_OK) return rc;
     }
-    // episode sink: a kernel that does not fold in-kernel leaves it to the
-    // group fold of its output rows below (the same arithmetic, kernels.hpp EpSink)
-    if (h->cm.ep_ret && h->N && !reward)
-        return fail(h, INVSIM_EINVAL, "the episode sink folds the reward outputs: pass reward / terminated / truncated");
     bool sunk = false;
     hipError_t e = hipSuccess;
     switch (h->family) {
@@ -1017,14 +1042,18 @@ static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, do
         if (e != hipSuccess) return hip_fail(h, e, "episode sink fold");
     }
     if (h->demand_stream == INVSIM_DEMAND_PHILOX) h->ph_step += (uint64_t)K;   // one counter value per launch step
-    if (h->t_known) {
+    if (h->t_known)
         for (int k = 0; k < K; k++) h->t_cur = next_period(h->t_cur, h->horizon, h->cm.autoreset, h->past_ok);
-    } else if (h->cm.autoreset == AR_DISABLED && !h->past_ok) {
+    return INVSIM_OK;
+}
+
+static int steps_end(invsim_handle *h, hipStream_t s) {
+    if (!h->t_known && h->cm.autoreset == AR_DISABLED && !h->past_ok) {
         // per-env periods (after a masked reset): the kernels skip an env stepped
         // past its horizon and flag it; surface that now, as the reference's
         // IndexError (inventory_management.py:267), at the cost of one sync
         uint32_t flags = 0;
-        e = hipMemcpyAsync(&flags, h->cm.status, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        hipError_t e = hipMemcpyAsync(&flags, h->cm.status, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(h, e, "status read");
         if (flags & 1u) {
@@ -1036,6 +1065,14 @@ static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, do
         }
     }
     return INVSIM_OK;
+}
+
+static int run_steps(invsim_handle *h, int K, const void *actions, void *obs, double *reward,
+                     uint8_t *terminated, uint8_t *truncated, void *final_obs, hipStream_t s,
+                     const PolicyIO *pol = nullptr) {
+    if (int rc = steps_begin(h, K, reward, s)) return rc;
+    if (int rc = steps_launch(h, K, actions, obs, reward, terminated, truncated, final_obs, s, pol)) return rc;
+    return steps_end(h, s);
 }
 
 int invsim_step(invsim_handle *h, const void *actions, void *obs, double *reward, uint8_t *terminated,
@@ -1076,6 +1113,25 @@ int invsim_metrics_dim(const invsim_handle *h, int32_t *dim) {
     if (!h || !dim) return fail(nullptr, INVSIM_EINVAL, "null argument");
     *dim = metrics_dim(h);
     return INVSIM_OK;
+}
+
+// what invsim_rollout_metrics and invsim_rollout_mlp refuse alike
+static int metric_rollout_checks(invsim_handle *h, const double *reward, const uint8_t *terminated,
+                                 const uint8_t *truncated) {
+    if (h->cm.autoreset == AR_SAME_STEP)
+        return fail(h, INVSIM_EINVAL, "metric rollouts do not return final_obs: use NEXT_STEP or DISABLED autoreset");
+    if ((reward == nullptr) != (terminated == nullptr) || (reward == nullptr) != (truncated == nullptr))
+        return fail(h, INVSIM_EINVAL, "reward, terminated and truncated are given together or not at all");
+    return INVSIM_OK;
+}
+
+// the EXT run kernels: the policy bookkeeping, the actions of StepIO::act
+static PolicyIO external_policy(const invsim_handle *h, double *metrics) {
+    PolicyIO p{};
+    p.kind = POL_EXTERNAL;
+    p.metrics = metrics;
+    p.mdim = metrics_dim(h);
+    return p;
 }
 
 // the RANDOM kind's PolicyIO fields: the upper bounds `high` (host, [action_dim]
@@ -1159,17 +1215,197 @@ int invsim_rollout_metrics(invsim_handle *h, int32_t K, const void *actions, voi
     if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
     if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
     if (K == 0) return INVSIM_OK;
-    if (h->cm.autoreset == AR_SAME_STEP)
-        return fail(h, INVSIM_EINVAL, "metric rollouts do not return final_obs: use NEXT_STEP or DISABLED autoreset");
     if (h->N && !actions) return fail(h, INVSIM_EINVAL, "null actions");
-    if ((reward == nullptr) != (terminated == nullptr) || (reward == nullptr) != (truncated == nullptr))
-        return fail(h, INVSIM_EINVAL, "reward, terminated and truncated are given together or not at all");
-    PolicyIO p{};
-    p.kind = POL_EXTERNAL;   // the EXT run kernels: the policy bookkeeping, the actions of StepIO::act
-    p.metrics = metrics;
-    p.mdim = metrics_dim(h);
+    if (int rc = metric_rollout_checks(h, reward, terminated, truncated)) return rc;
+    const PolicyIO p = external_policy(h, metrics);
     DeviceGuard g(h->device);
     return run_steps(h, K, actions, obs, reward, terminated, truncated, nullptr, (hipStream_t)stream, &p);
+}
+
+// ------------------------------------------------------------------ MLP actor
+int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **out) {
+    if (!h || !sp || !out) return fail(h, INVSIM_EINVAL, "null argument");
+    *out = nullptr;
+    if (int rc = refuse_in_capture(h, "mlp_create")) return rc;
+    const int n = sp->n_layers;
+    if (n < 1 || n > INVSIM_MLP_MAX_LAYERS)
+        return fail(h, INVSIM_ERANGE, "n_layers must be 1.." + std::to_string(INVSIM_MLP_MAX_LAYERS));
+    if (!sp->dims || !sp->weight) return fail(h, INVSIM_EINVAL, "null dims / weight");
+    if (sp->dims[0] != h->obs_dim || sp->dims[n] != h->act_dim)
+        return fail(h, INVSIM_ERANGE, "dims[0] / dims[n_layers] must be the handle's obs_dim " + std::to_string(h->obs_dim) +
+                                          " / action_dim " + std::to_string(h->act_dim));
+    if (h->obs_dim > INVSIM_MLP_MAX_WIDTH) return fail(h, INVSIM_ERANGE, "obs_dim too large for an MLP actor");
+    if (h->act_dim > INVSIM_POLICY_MAX_ACTION) return fail(h, INVSIM_ERANGE, "action_dim too large for an MLP actor");
+    for (int l = 1; l < n; l++)
+        if (sp->dims[l] < 1 || sp->dims[l] > INVSIM_MLP_MAX_WIDTH)
+            return fail(h, INVSIM_ERANGE, "hidden widths must be 1.." + std::to_string(INVSIM_MLP_MAX_WIDTH));
+    if (n > 1 && sp->activation != INVSIM_MLP_RELU && sp->activation != INVSIM_MLP_TANH)
+        return fail(h, INVSIM_EINVAL, "hidden activation must be INVSIM_MLP_RELU or INVSIM_MLP_TANH");
+    if (sp->out_activation != INVSIM_MLP_NONE && sp->out_activation != INVSIM_MLP_TANH)
+        return fail(h, INVSIM_EINVAL, "out_activation must be INVSIM_MLP_NONE or INVSIM_MLP_TANH");
+    if ((sp->in_scale == nullptr) != (sp->in_shift == nullptr) || (sp->out_scale == nullptr) != (sp->out_shift == nullptr))
+        return fail(h, INVSIM_EINVAL, "scale and shift are given in pairs");
+    if (sp->clip && (!sp->low || !sp->high)) return fail(h, INVSIM_EINVAL, "clip needs the action bounds low / high");
+    for (int l = 0; l < n; l++)
+        if (!sp->weight[l]) return fail(h, INVSIM_EINVAL, "null weight matrix");
+
+    // one blob of 8-byte slots: per layer the transposed weights [in][opad] and the
+    // bias [opad], then the scales and the bounds
+    const bool i64 = h->family == INVSIM_INVMGMT;
+    const int O = h->obs_dim, A = h->act_dim;
+    auto m = new invsim_mlp();
+    m->owner = h;
+    MlpDev &d = m->dev;
+    d.n_layers = n;
+    d.act = n > 1 ? sp->activation : INVSIM_MLP_NONE;
+    d.out_act = sp->out_activation;
+    d.clip = sp->clip ? 1 : 0;
+    std::vector<float> blob;
+    auto reserve = [&blob](size_t floats) {          // returns the offset; keeps 8-byte alignment
+        const size_t off = blob.size();
+        blob.resize(off + (floats + 1) / 2 * 2, 0.0f);
+        return off;
+    };
+    size_t o_wt[MLP_LAYERS], o_b[MLP_LAYERS], o_is = 0, o_ih = 0, o_os = 0, o_oh = 0, o_lo = 0, o_hi = 0;
+    d.rows = 0;
+    for (int l = 0; l <= n; l++) {
+        d.dims[l] = sp->dims[l];
+        d.rows = std::max(d.rows, sp->dims[l]);
+    }
+    for (int l = 0; l < n; l++) {
+        const int in = d.dims[l], outn = d.dims[l + 1], opad = (outn + 3) / 4 * 4;
+        d.opad[l] = opad;
+        o_wt[l] = reserve((size_t)in * opad);
+        for (int j = 0; j < outn; j++)
+            for (int i = 0; i < in; i++) blob[o_wt[l] + (size_t)i * opad + j] = sp->weight[l][(size_t)j * in + i];
+        o_b[l] = reserve(opad);
+        if (sp->bias && sp->bias[l]) std::copy(sp->bias[l], sp->bias[l] + outn, blob.begin() + o_b[l]);
+    }
+    const int apad = d.opad[n - 1];
+    if (sp->in_scale) {
+        o_is = reserve(O), o_ih = reserve(O);
+        std::copy(sp->in_scale, sp->in_scale + O, blob.begin() + o_is);
+        std::copy(sp->in_shift, sp->in_shift + O, blob.begin() + o_ih);
+    }
+    if (sp->out_scale) {
+        o_os = reserve(apad), o_oh = reserve(apad);
+        std::copy(sp->out_scale, sp->out_scale + A, blob.begin() + o_os);
+        std::copy(sp->out_shift, sp->out_shift + A, blob.begin() + o_oh);
+    }
+    if (sp->clip) {      // f32 spaces: the bounds; int64 spaces: the bounds as f64 (the clamp runs in f64)
+        o_lo = reserve(2 * (size_t)A), o_hi = reserve(2 * (size_t)A);
+        for (int a = 0; a < A; a++) {
+            if (i64) {
+                const double lo = (double)((const int64_t *)sp->low)[a], hi = (double)((const int64_t *)sp->high)[a];
+                std::memcpy(&blob[o_lo + 2 * a], &lo, 8);
+                std::memcpy(&blob[o_hi + 2 * a], &hi, 8);
+            } else {
+                blob[o_lo + a] = ((const float *)sp->low)[a];
+                blob[o_hi + a] = ((const float *)sp->high)[a];
+            }
+        }
+    }
+    const size_t o_dev = reserve((sizeof(MlpDev) + 3) / 4);
+    DeviceGuard g(h->device);
+    const size_t esz = i64 ? 8 : 4;
+    const size_t n_el = (size_t)std::max<int64_t>(h->N, 1);
+    hipError_t e = mlp_prepare();
+    if (e == hipSuccess) e = hipMalloc(&m->blob, blob.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&m->obs_row, n_el * O * esz);
+    if (e == hipSuccess) e = hipMalloc(&m->act_row, n_el * A * esz);
+    if (e == hipSuccess) {
+        const float *base = m->blob;
+        for (int l = 0; l < n; l++) {
+            d.wt[l] = base + o_wt[l];
+            d.bias[l] = base + o_b[l];
+        }
+        if (sp->in_scale) d.in_scale = base + o_is, d.in_shift = base + o_ih;
+        if (sp->out_scale) d.out_scale = base + o_os, d.out_shift = base + o_oh;
+        if (sp->clip) {
+            d.lo_f = base + o_lo, d.hi_f = base + o_hi;
+            d.lo_d = (const double *)(base + o_lo), d.hi_d = (const double *)(base + o_hi);
+        }
+        std::memcpy(&blob[o_dev], &d, sizeof(MlpDev));
+        m->dev_copy = (const MlpDev *)(base + o_dev);
+        e = hipMemcpy(m->blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        mlp_free(m);
+        return fail(h, e == hipErrorOutOfMemory ? INVSIM_ENOMEM : INVSIM_EDEVICE,
+                    std::string("mlp_create: ") + hipGetErrorString(e));
+    }
+    *out = m;
+    return INVSIM_OK;
+}
+
+void invsim_mlp_destroy(invsim_mlp *m) {
+    if (!m) return;
+    if (m->owner->capturing) {     // hipFree synchronises: the object stays valid
+        (void)refuse_in_capture(m->owner, "mlp_destroy");
+        return;
+    }
+    DeviceGuard g(m->owner->device);
+    mlp_free(m);
+}
+
+int invsim_mlp_actions(invsim_handle *h, const invsim_mlp *m, const void *obs, void *actions, float *raw,
+                       void *stream) {
+    TraceRange tr_("invsim_mlp_actions");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (h->N && !obs) return fail(h, INVSIM_EINVAL, "null obs");
+    DeviceGuard g(h->device);
+    hipError_t e = mlp_launch(m->dev, m->dev_copy, h->family == INVSIM_INVMGMT, obs, actions, raw, h->N, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp launch");
+}
+
+int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0, void *obs, double *reward,
+                       uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream) {
+    TraceRange tr_("invsim_rollout_mlp");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
+    if (K == 0) return INVSIM_OK;
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (h->N && !obs0) return fail(h, INVSIM_EINVAL, "null obs0: the network's first input is the observation the env "
+                                                     "last returned");
+    if (int rc = metric_rollout_checks(h, reward, terminated, truncated)) return rc;
+    const PolicyIO p = external_policy(h, metrics);
+    const bool i64 = h->family == INVSIM_INVMGMT;
+    const size_t o_row = (size_t)h->N * h->obs_dim * (i64 ? 8 : 4), a_row = (size_t)h->N * h->act_dim * (i64 ? 8 : 4);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard g(h->device);
+    if (int rc = steps_begin(h, K, reward, s)) return rc;
+    // episode sink: the call's K output rows are folded once, after the loop, as
+    // one invsim_rollout_metrics launch of K steps folds them (K folds of one row
+    // each add to part in another order); the one-step launches run without it
+    struct SinkOff {
+        invsim_handle *h;
+        double *ret, *part;
+        explicit SinkOff(invsim_handle *h_) : h(h_), ret(h_->cm.ep_ret), part(h_->cm.ep_part) { set(nullptr, nullptr); }
+        ~SinkOff() { set(ret, part); }
+        void set(double *r, double *p) {
+            if (!ret) return;
+            h->cm.ep_ret = r, h->cm.ep_part = p;
+            sync_common(h);
+        }
+    } sink(h);
+    const void *in = obs0;
+    for (int k = 0; k < K; k++) {
+        void *a_k = actions ? (char *)actions + k * a_row : m->act_row;
+        void *o_k = obs ? (char *)obs + k * o_row : m->obs_row;   // in == o_k then: read before it is overwritten (stream order)
+        hipError_t e = mlp_launch(m->dev, m->dev_copy, i64, in, a_k, nullptr, h->N, s);
+        if (e != hipSuccess) return hip_fail(h, e, "mlp launch");
+        const size_t r = (size_t)k * h->N;
+        if (int rc = steps_launch(h, 1, a_k, o_k, reward ? reward + r : nullptr, terminated ? terminated + r : nullptr,
+                                  truncated ? truncated + r : nullptr, nullptr, s, &p))
+            return rc;
+        in = o_k;
+    }
+    if (sink.ret && h->N) {      // (steps_begin made sure of the reward triple)
+        hipError_t e = episode_fold_groups_launch(reward, terminated, truncated, K, h->N, sink.ret, sink.part, s);
+        if (e != hipSuccess) return hip_fail(h, e, "episode sink fold");
+    }
+    return steps_end(h, s);
 }
 
 int invsim_action_rng_bytes(const invsim_handle *h, int64_t *bytes) {

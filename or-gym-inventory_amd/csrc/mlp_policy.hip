@@ -1,0 +1,174 @@
+// In-library MLP actor: observations in, actions out, one launch
+// (include/invsim.h "MLP actor" states the arithmetic op by op; every
+// multiply-add below is an explicit fmaf and nothing else adds or multiplies).
+//
+// Layout.  One workgroup = 64 envs x 4 waves (8 for wide networks:
+// mlp_threads); lane = env in every wave.  The
+// activations of a layer live in LDS as [unit][MLP_ROW] floats (lane reads of
+// one unit: 64 consecutive words), two buffers, one workgroup barrier per
+// layer.  A layer's output units are cut into chunks of 16 (then of 4 for the
+// last 1..15) and dealt to the waves round-robin; a wave keeps a chunk's
+// accumulators in VGPRs and walks the inputs in ascending order: read x[i]
+// once from LDS, one FMA per owned unit, which is the contract's order for
+// every unit.  The weights of one input are contiguous over the units (the
+// device copy is transposed and zero padded to a multiple of 4), indexed by
+// wave-uniform values only and read through constant-address-space pointers,
+// so they arrive by scalar loads and feed the FMA from SGPRs.  A padded unit is computed (its weights are 0) and dropped: it
+// is never stored, so it never enters a sum.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "../../include/invsim.h"
+#include "mlp_policy.hpp"
+
+namespace invsim {
+namespace {
+
+// The parameter blob is written once, before any launch, and only read by the
+// kernels: pointers into it are taken in the constant address space, so every
+// wave-uniform read of it (the argument block, weights, biases, output scales)
+// is a scalar load whatever the compiler can prove about aliasing.
+#define MLP_CONST __attribute__((address_space(4)))
+typedef const float MLP_CONST *mlp_cfloat;
+typedef const MlpDev MLP_CONST &mlp_cdev;
+template <typename T>
+__device__ __forceinline__ const T MLP_CONST *mlp_const(const T *p) {
+    return (const T MLP_CONST *)(uintptr_t)p;
+}
+
+__device__ __forceinline__ float mlp_activate(float v, int kind) {
+    if (kind == INVSIM_MLP_RELU) return v > 0.0f ? v : 0.0f;   // NaN -> +0.0f
+    if (kind == INVSIM_MLP_TANH) return tanhf(v);
+    return v;
+}
+
+// CH output units base .. base + CH - 1 of layer l for this wave's 64 envs
+template <int CH>
+__device__ __forceinline__ void mlp_chunk(mlp_cdev m, int l, int base, const float *xin, float *xout, int lane) {
+    const int in = m.dims[l], out = m.dims[l + 1], opad = m.opad[l];
+    const bool last = l == m.n_layers - 1;
+    mlp_cfloat w = mlp_const(m.wt[l]) + base;
+    mlp_cfloat b = mlp_const(m.bias[l]) + base;
+    mlp_cfloat osc = mlp_const(m.out_scale), osh = mlp_const(m.out_shift);
+    float acc[CH];
+#pragma unroll
+    for (int u = 0; u < CH; u++) acc[u] = b[u];
+    const float *x = xin + lane;
+#pragma unroll 4
+    for (int i = 0; i < in; i++, w += opad, x += MLP_ROW) {
+        const float xi = *x;
+#pragma unroll
+        for (int u = 0; u < CH; u++) acc[u] = __builtin_fmaf(w[u], xi, acc[u]);
+    }
+    const int kind = last ? m.out_act : m.act;
+    const bool scale = last && m.out_scale;
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        if (base + u < out) {        // wave-uniform
+            float v = mlp_activate(acc[u], kind);
+            if (scale) v = __builtin_fmaf(v, osc[base + u], osh[base + u]);
+            xout[(base + u) * MLP_ROW + lane] = v;
+        }
+    }
+}
+
+// invsim.policies.convert_actions, f32 spaces
+__device__ __forceinline__ float mlp_convert(float r, float lo, float hi, bool clip) {
+    if (!clip) return r;
+    const bool nan = r != r;
+    const float x = (r > lo || nan) ? r : lo;
+    return (x < hi || nan) ? x : hi;
+}
+
+// invsim.policies.convert_actions, int64 spaces: in f64
+__device__ __forceinline__ long long mlp_convert(float r, double lo, double hi, bool clip) {
+    double x = (double)r;
+    if (clip) {
+        x = x < lo ? lo : x;
+        x = x > hi ? hi : x;
+    }
+    if (x != x) x = 0.0;
+    return (long long)x;     // toward zero
+}
+
+template <bool I64>
+__global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restrict__ mp, const void *__restrict__ obs_,
+                                                         void *__restrict__ act_, float *__restrict__ raw, int64_t N) {
+    mlp_cdev m = *mlp_const(mp);
+    using Obs = typename std::conditional<I64, long long, float>::type;
+    extern __shared__ float mlp_lds[];
+    const int half = m.rows * MLP_ROW;     // floats of one buffer; layer l reads buffer l & 1
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), waves = blockDim.x >> 6, threads = blockDim.x;
+    const int64_t env0 = (int64_t)blockIdx.x * MLP_ENVS;
+
+    // input: this workgroup's 64 obs rows are one contiguous block of [N][O]
+    {
+        const int O = m.dims[0];
+        const Obs *obs = (const Obs *)obs_ + env0 * O;
+        const int64_t left = (N - env0) * O;       // elements of envs < N from here on (> 0)
+        for (int e = tid; e < MLP_ENVS * O; e += threads) {
+            const int env = e / O, i = e - env * O;
+            float x = 0.0f;                        // lanes at or past N compute on zeros and store nothing
+            if (e < left) {
+                x = (float)obs[e];
+                if (m.in_scale) x = __builtin_fmaf(x, m.in_scale[i], m.in_shift[i]);
+            }
+            mlp_lds[i * MLP_ROW + env] = x;
+        }
+    }
+    __syncthreads();
+
+    for (int l = 0; l < m.n_layers; l++) {
+        const int out = m.dims[l + 1];
+        const int n16 = out >> 4, n4 = ((out & 15) + 3) >> 2;
+        const float *xin = mlp_lds + (l & 1) * half;
+        float *xout = mlp_lds + ((l + 1) & 1) * half;
+        for (int c = wave; c < n16 + n4; c += waves) {
+            if (c < n16) mlp_chunk<16>(m, l, 16 * c, xin, xout, lane);
+            else mlp_chunk<4>(m, l, 16 * n16 + 4 * (c - n16), xin, xout, lane);
+        }
+        __syncthreads();
+    }
+
+    // output: [N][A] rows of this workgroup's envs, contiguous again
+    const int A = m.dims[m.n_layers];
+    const float *res = mlp_lds + (m.n_layers & 1) * half;
+    const int64_t left = (N - env0) * A;
+    for (int e = tid; e < MLP_ENVS * A && e < left; e += threads) {
+        const int env = e / A, a = e - env * A;
+        const float r = res[a * MLP_ROW + env];
+        const int64_t g = env0 * A + e;
+        if (raw) raw[g] = r;
+        if (act_) {
+            if (I64) ((long long *)act_)[g] = mlp_convert(r, m.clip ? m.lo_d[a] : 0.0, m.clip ? m.hi_d[a] : 0.0, m.clip != 0);
+            else ((float *)act_)[g] = mlp_convert(r, m.clip ? m.lo_f[a] : 0.0f, m.clip ? m.hi_f[a] : 0.0f, m.clip != 0);
+        }
+    }
+}
+
+constexpr int MLP_LDS_MAX = 2 * MLP_WIDTH * MLP_ROW * (int)sizeof(float);   // 133 120 B of the CU's 160 KiB
+
+}  // namespace
+
+hipError_t mlp_prepare() {
+    hipError_t e = hipFuncSetAttribute((const void *)mlp_policy_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       MLP_LDS_MAX);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)mlp_policy_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               MLP_LDS_MAX);
+}
+
+hipError_t mlp_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw, int64_t N,
+                      hipStream_t s) {
+    if (N <= 0 || (!actions && !raw)) return hipSuccess;
+    const size_t lds = mlp_lds_bytes(m);
+    if (lds > (size_t)MLP_LDS_MAX) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((N + MLP_ENVS - 1) / MLP_ENVS)), block(mlp_threads(m));
+    if (i64) hipLaunchKernelGGL(mlp_policy_kernel<true>, grid, block, lds, s, dev, obs, actions, raw, N);
+    else hipLaunchKernelGGL(mlp_policy_kernel<false>, grid, block, lds, s, dev, obs, actions, raw, N);
+    return hipGetLastError();
+}
+
+}  // namespace invsim

@@ -28,6 +28,7 @@ _LAZY = {
     "sSPolicyAgent": "policies",
     "RandomAgent": "policies",
     "TorchPolicyAgent": "policies",
+    "MLPPolicyAgent": "policies",
     "convert_actions": "policies",
     "evaluate_agent": "policies",
     "rollout_policy": "policies",

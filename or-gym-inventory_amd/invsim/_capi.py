@@ -31,6 +31,7 @@ EXPORTS = (
     "invsim_episode_fold_groups", "invsim_set_episode_sink",
     "invsim_action_rng_bytes", "invsim_seed_action_rng", "invsim_set_action_rng", "invsim_sample_actions",
     "invsim_rollout_metrics",
+    "invsim_mlp_create", "invsim_mlp_destroy", "invsim_mlp_actions", "invsim_rollout_mlp",
 )
 ABI_VERSION = 4
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
@@ -70,6 +71,18 @@ POLICY_KINDS = {"constant": 1, "base_stock": 2, "order_up_to": 3, "classic_nv": 
 class PolicySpec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("variant", C.c_int32), ("safety_factor", C.c_double),
                 ("mu", C.c_double), ("constant", C.c_void_p)]
+
+
+MLP_ACTIVATIONS = {None: 0, "none": 0, "relu": 1, "tanh": 2}
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 5, 256
+
+
+class MLPSpec(C.Structure):
+    """invsim_mlp_spec"""
+    _fields_ = [("n_layers", C.c_int32), ("activation", C.c_int32), ("out_activation", C.c_int32),
+                ("clip", C.c_int32), ("dims", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p),
+                ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("out_scale", C.c_void_p),
+                ("out_shift", C.c_void_p), ("low", C.c_void_p), ("high", C.c_void_p)]
 
 
 class InvsimError(RuntimeError):
@@ -121,6 +134,10 @@ def _declare(lib):
         "invsim_seed_action_rng": ([H, P, U64, U64, I64, P], C.c_int),
         "invsim_set_action_rng": ([H, P], C.c_int),
         "invsim_sample_actions": ([H, I32, P, P, P], C.c_int),
+        "invsim_mlp_create": ([H, P, P], C.c_int),
+        "invsim_mlp_destroy": ([P], None),
+        "invsim_mlp_actions": ([H, P, P, P, P, P], C.c_int),
+        "invsim_rollout_mlp": ([H, I32, P, P, P, P, P, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -29,7 +29,11 @@ through ``TorchPolicyAgent(fn)``: the network runs in torch on the env's device
 and stream between one-step ``invsim_rollout_metrics`` launches, which keep the
 same per-env sums for the actions they are handed, so ``rollout_policy`` and
 ``evaluate_agent`` take the agent like any other; ``convert_actions`` is the
-wrapper's post-processing of the network's output.
+wrapper's post-processing of the network's output.  A plain feed-forward actor
+(Linear / ReLU / Tanh, at most 5 layers of at most 256 units) can instead be
+handed to the library as an ``MLPPolicyAgent``: the network is then a HIP
+kernel of its own and the closed loop is issued in C (``invsim_rollout_mlp``),
+two launches per step with no Python between them.
 
 ``evaluate_agent(agent, env_cls, env_config, n_episodes, seed_offset)`` returns
 the reference's summary columns (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -280,15 +284,185 @@ def _rollout_torch(env, agent, K, obs, rewards, actions, metrics, obs0):
     return out
 
 
+def _f32(a, shape, what):
+    """a parameter as a contiguous float32 host array of the given shape"""
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    if shape is not None and a.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+class MLPPolicyAgent(_Agent):
+    """A trained feed-forward actor evaluated by the library itself: one HIP
+    kernel per step takes the observations to actions, and the closed loop
+    (network, env step, network, ...) is issued in C on the env's stream
+    (``invsim_rollout_mlp``), two launches per step with no Python in between.
+    The arithmetic is defined op by op in ``include/invsim.h`` ("MLP actor"):
+    float32 ``fmaf`` chains in ascending input order, so a ReLU or linear
+    network is reproducible bit for bit on a CPU (``tests/mlp_model.py``); a
+    tanh network is defined up to the device's ``tanhf``.
+
+    ``layers``: a list of ``(weight, bias)`` pairs, ``weight`` ``[out, in]`` as
+    ``torch.nn.Linear.weight``, ``bias`` ``[out]`` or ``None``; at most 5 linear
+    layers, hidden widths at most 256 (wider actors: ``TorchPolicyAgent``).
+    ``activation`` ("relu" / "tanh") follows every layer but the last,
+    ``out_activation`` (``None`` / "tanh") the last.  ``in_scale`` / ``in_shift``
+    ``[obs_dim]`` normalise the observations (``x * scale + shift``, fused);
+    ``out_scale`` / ``out_shift`` ``[action_dim]`` rescale the outputs, e.g. a
+    squashed actor's ``low + 0.5 * (tanh + 1) * (high - low)`` is ``out_scale =
+    0.5 * (high - low)``, ``out_shift = low + out_scale``.  The result goes
+    through ``convert_actions`` (``clip=False``: cast only).
+
+    ``rollout_policy`` / ``evaluate_agent`` take it like a ``TorchPolicyAgent``
+    (``obs0`` required, the same returned dict); ``env.mlp_actions(agent, obs)``
+    is the single launch.  The device copy is built once per env and freed
+    with it."""
+
+    def __init__(self, layers, activation="tanh", out_activation=None, in_scale=None, in_shift=None,
+                 out_scale=None, out_shift=None, clip=True, name="MLP"):
+        layers = list(layers)
+        if not 1 <= len(layers) <= _capi.MLP_MAX_LAYERS:
+            raise ValueError(f"an MLPPolicyAgent has 1..{_capi.MLP_MAX_LAYERS} linear layers, got {len(layers)}")
+        if activation not in ("relu", "tanh"):
+            raise ValueError("activation must be 'relu' or 'tanh'")
+        if out_activation not in (None, "none", "tanh"):
+            raise ValueError("out_activation must be None or 'tanh'")
+        if (in_scale is None) != (in_shift is None) or (out_scale is None) != (out_shift is None):
+            raise ValueError("scale and shift are given in pairs")
+        self.weights, self.biases = [], []
+        for l, (w, b) in enumerate(layers):
+            w = _f32(w, None, "weight")
+            if w.ndim != 2 or 0 in w.shape:
+                raise ValueError(f"layer {l}: weight must be [out, in], got {w.shape}")
+            if self.weights and w.shape[1] != self.weights[-1].shape[0]:
+                raise ValueError(f"layer {l}: weight {w.shape} does not take the {self.weights[-1].shape[0]} outputs "
+                                 "of the layer before")
+            self.weights.append(w)
+            self.biases.append(None if b is None else _f32(b, (w.shape[0],), f"layer {l}: bias"))
+        self.dims = [self.weights[0].shape[1]] + [w.shape[0] for w in self.weights]
+        if any(d > _capi.MLP_MAX_WIDTH for d in self.dims[1:-1]):
+            raise ValueError(f"hidden widths are at most {_capi.MLP_MAX_WIDTH}, got {self.dims[1:-1]} "
+                             "(a wider actor runs through TorchPolicyAgent)")
+        O, A = self.dims[0], self.dims[-1]
+        self.in_scale = None if in_scale is None else _f32(in_scale, (O,), "in_scale")
+        self.in_shift = None if in_shift is None else _f32(in_shift, (O,), "in_shift")
+        self.out_scale = None if out_scale is None else _f32(out_scale, (A,), "out_scale")
+        self.out_shift = None if out_shift is None else _f32(out_shift, (A,), "out_shift")
+        self.activation = activation
+        self.out_activation = None if out_activation in (None, "none") else out_activation
+        self.clip = bool(clip)
+        self.name = name
+        self._objs = weakref.WeakKeyDictionary()      # env -> (its handle, the invsim_mlp built for it)
+
+    @classmethod
+    def from_module(cls, module, **kw):
+        """From an ``nn.Sequential`` of ``Linear`` / ``ReLU`` / ``Tanh`` (SB3's
+        ``mlp_extractor.policy_net`` followed by ``action_net``, flattened into
+        one Sequential): a Linear, then activation and Linear alternating, an
+        optional activation at the end (which must be Tanh).  The parameters are
+        copied as float32.  Anything else, or two different hidden activations,
+        is a TypeError.  Other arguments go to the constructor."""
+        nn = torch.nn
+        if not isinstance(module, nn.Sequential):
+            raise TypeError("from_module takes an nn.Sequential of Linear / ReLU / Tanh")
+        layers, acts = [], []         # acts[i]: the activation after linear layer i, or None
+        for m in module:
+            if isinstance(m, nn.Linear):
+                if len(acts) < len(layers):
+                    raise TypeError("two Linear layers without an activation between them")
+                layers.append((m.weight, m.bias))
+            elif isinstance(m, (nn.ReLU, nn.Tanh)):
+                if len(acts) >= len(layers):
+                    raise TypeError("an activation must follow a Linear layer")
+                acts.append("relu" if isinstance(m, nn.ReLU) else "tanh")
+            else:
+                raise TypeError(f"from_module: unsupported module {type(m).__name__} (Linear, ReLU and Tanh only)")
+        if not layers:
+            raise TypeError("from_module: no Linear layer")
+        out_act = acts.pop() if len(acts) == len(layers) else None
+        if out_act == "relu":
+            raise TypeError("from_module: the output activation is none or Tanh")
+        if len(set(acts)) > 1:
+            raise TypeError("from_module: mixed hidden activations (one kind per network)")
+        if "activation" in kw or "out_activation" in kw:
+            raise TypeError("from_module reads the activations from the module")
+        return cls(layers, activation=acts[0] if acts else "tanh", out_activation=out_act, **kw)
+
+    def device_spec(self, env):
+        raise TypeError("MLPPolicyAgent runs in its own kernel: use rollout_policy / evaluate_agent / env.mlp_actions")
+
+    def device_object(self, env):
+        """The ``invsim_mlp`` of this network on ``env`` (built at the first call;
+        synchronises then: under ``env.capture`` let the agent meet the env first)."""
+        hit = self._objs.get(env)
+        if hit is not None and hit[0] is env._h:
+            return hit[1]
+        if self.dims[0] != env.obs_dim or self.dims[-1] != env.action_dim:
+            raise ValueError(f"the network maps {self.dims[0]} -> {self.dims[-1]}, the env needs "
+                             f"{env.obs_dim} -> {env.action_dim}")
+        n = len(self.weights)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        dims = np.asarray(self.dims, np.int32)
+        W = (C.c_void_p * n)(*[w.ctypes.data for w in self.weights])
+        B = (C.c_void_p * n)(*[ptr(b) for b in self.biases])
+        sp = env.single_action_space
+        low = np.ascontiguousarray(np.asarray(sp.low, dtype=sp.dtype).reshape(-1))
+        high = np.ascontiguousarray(np.asarray(sp.high, dtype=sp.dtype).reshape(-1))
+        spec = _capi.MLPSpec(n, _capi.MLP_ACTIVATIONS[self.activation], _capi.MLP_ACTIVATIONS[self.out_activation],
+                             int(self.clip), dims.ctypes.data, C.cast(W, C.c_void_p), C.cast(B, C.c_void_p),
+                             ptr(self.in_scale), ptr(self.in_shift), ptr(self.out_scale), ptr(self.out_shift),
+                             low.ctypes.data, high.ctypes.data)
+        obj = C.c_void_p()
+        _capi.check(env._lib.invsim_mlp_create(env._h, C.byref(spec), C.byref(obj)), env._h, "mlp_create")
+        env._mlps.append(obj)            # the env destroys it in close(), before its handle
+        self._objs[env] = (env._h, obj)
+        return obj
+
+
+def _rollout_mlp(env, agent, K, obs, rewards, actions, metrics, obs0):
+    """The closed loop of an MLPPolicyAgent: one invsim_rollout_mlp call."""
+    if obs0 is None:
+        raise ValueError("an MLPPolicyAgent rollout needs obs0, the observation the env last returned "
+                         "(reset()'s, or the last row of the previous rollout's obs)")
+    N, dev = env.num_envs, env.device
+    obs0 = torch.as_tensor(obs0, device=dev)
+    if tuple(obs0.shape) != (N, env.obs_dim):
+        raise ValueError(f"obs0 must have shape {(N, env.obs_dim)}, got {tuple(obs0.shape)}")
+    obs0 = obs0.to(env.obs_dtype).contiguous()
+    metrics = env._metrics_arg(metrics)
+    obj = agent.device_object(env)
+    out = {}
+    o = torch.empty((K, N, env.obs_dim), dtype=env.obs_dtype, device=dev) if obs else None
+    if rewards:
+        out["reward"] = torch.empty((K, N), dtype=torch.float64, device=dev)
+        out["terminated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+        out["truncated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+    a = torch.empty((K, N, env.action_dim), dtype=env.act_dtype, device=dev) if actions else None
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _capi.check(env._lib.invsim_rollout_mlp(
+        env._h, int(K), obj, obs0.data_ptr(), p(o), p(out.get("reward")), p(out.get("terminated")),
+        p(out.get("truncated")), p(a), p(metrics), env._stream()), env._h, "rollout_mlp")
+    if obs:
+        out["obs"] = o
+    if actions:
+        out["actions"] = a
+    return out
+
+
 def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metrics=None, obs0=None):
     """K steps of every env of ``env`` under ``agent``.  Returns a dict with
     the requested device tensors; ``metrics`` (float64 [N, M]) is accumulated in
     place when given.  The heuristic agents run in the step kernel, one launch;
-    a ``TorchPolicyAgent`` runs in torch between K one-step launches and needs
-    ``obs0``, the observation the env last returned (``actions`` then records
-    what the policy produced at every step, reset steps included)."""
+    a ``TorchPolicyAgent`` runs in torch between K one-step launches and an
+    ``MLPPolicyAgent`` in a kernel of its own before each; both need ``obs0``,
+    the observation the env last returned (``actions`` then records what the
+    policy produced at every step, reset steps included)."""
     if isinstance(agent, TorchPolicyAgent):
         return _rollout_torch(env, agent, int(K), obs, rewards, actions, metrics, obs0)
+    if isinstance(agent, MLPPolicyAgent):
+        return _rollout_mlp(env, agent, int(K), obs, rewards, actions, metrics, obs0)
     spec, keep = agent.device_spec(env)
     N, dev = env.num_envs, env.device
     out = {}
@@ -358,7 +532,8 @@ def _gather_rows(met, n_episodes, world, rank, group):
 def evaluate_agent(agent, env_cls, env_config=None, n_episodes=100, seed_offset=0, device=None, group=None):
     """Batched evaluate_agent: episode i = env i seeded seed_offset + i, one
     full episode under ``agent`` in one kernel launch (a ``TorchPolicyAgent``:
-    one launch per step, with the policy's torch ops between).  Returns a dict of
+    one launch per step, with the policy's torch ops between; an
+    ``MLPPolicyAgent``: two launches per step, issued by the library).  Returns a dict of
     per-episode columns (the reference's summary DataFrame columns).
 
     Under torch.distributed (one process per GPU) the episodes are sharded by

@@ -112,6 +112,7 @@ class InvSimVectorEnv:
             _capi.check(self._lib.invsim_set_info_record(self._h, self._rec.data_ptr()), self._h, "set_info_record")
         self._out = None
         self._arng = None     # RandomAgent's action generators (seed_actions)
+        self._mlps = []       # invsim_mlp objects of MLPPolicyAgents that met this env (destroyed in close)
 
     def _record_info(self, info):
         """Decode the per-step record into the reference's step-info names."""
@@ -326,6 +327,23 @@ class InvSimVectorEnv:
             out["obs"] = o
         return out
 
+    def mlp_actions(self, agent, obs, raw=False):
+        """One launch of an MLPPolicyAgent's network on obs [N, O] (the env's obs
+        dtype): the actions [N, A] in the action dtype, or with ``raw=True`` the
+        pair (actions, the float32 outputs before clipping and casting).  Env
+        state is not touched."""
+        o = torch.as_tensor(obs, device=self.device)
+        if tuple(o.shape) != (self.num_envs, self.obs_dim):
+            raise ValueError(f"obs must have shape {(self.num_envs, self.obs_dim)}, got {tuple(o.shape)}")
+        o = o.to(self.obs_dtype).contiguous()
+        obj = agent.device_object(self)
+        a = self._alloc(self.num_envs, self.action_dim, dtype=self.act_dtype)
+        r = self._alloc(self.num_envs, self.action_dim, dtype=torch.float32) if raw else None
+        _capi.check(self._lib.invsim_mlp_actions(self._h, obj, o.data_ptr(), a.data_ptr(),
+                                                 r.data_ptr() if raw else None, self._stream()),
+                    self._h, "mlp_actions")
+        return (a, r) if raw else a
+
     # -- RandomAgent's action stream (include/invsim.h "RandomAgent") ----------
     def _action_high(self):
         """The action space's upper bounds in the action dtype (host array)."""
@@ -464,6 +482,9 @@ class InvSimVectorEnv:
     def close(self):
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
+            for m in getattr(self, "_mlps", ()):
+                self._lib.invsim_mlp_destroy(m)
+            self._mlps = []
             self._lib.invsim_destroy(self._h)
             self._h = None
 

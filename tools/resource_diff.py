@@ -2,7 +2,7 @@
 """Compare the kernel resource usage of two builds, one remark log per
 translation unit (hipcc ... -Rpass-analysis=kernel-resource-usage -c X.hip 2> X.log).
 
-    tools/resource_diff.py PARENT_DIR NEW_DIR [--cxxfilt PATH] > resources.md
+    tools/resource_diff.py PARENT_DIR NEW_DIR [--cxxfilt PATH] [--plain] > resources.md
 
 Every kernel is keyed by (translation unit, demangled name).  Reports the
 kernels of the parent that are absent or differ in VGPRs, AGPRs, SGPRs, scratch,
@@ -11,6 +11,10 @@ instantiations beside the policy instantiation they are a variant of: the same
 template arguments with RND = EXT = false (the parent's name), or, for the
 InvMgmt translation unit invmgmt_ext, the kernel of the same name in invmgmt
 (Pcg) / invmgmt_ph (PhiloxGen).
+
+--plain: both builds already have the EXT template argument (every change after
+the one that added it): names are compared as they are, and the EXT table is
+left out.
 """
 import glob
 import os
@@ -80,7 +84,8 @@ def main():
     if "--cxxfilt" in sys.argv:
         cxxfilt = sys.argv[sys.argv.index("--cxxfilt") + 1]
         args.remove(cxxfilt)
-    old, new = parse(args[0], cxxfilt), parse(args[1], cxxfilt, parent_names=True)
+    plain = "--plain" in sys.argv
+    old, new = parse(args[0], cxxfilt), parse(args[1], cxxfilt, parent_names=not plain)
     same = [k for k in old if k in new and row(old[k]) == row(new[k])]
     diff = [k for k in old if k in new and row(old[k]) != row(new[k])]
     gone = [k for k in old if k not in new]
@@ -97,6 +102,8 @@ def main():
             print(f"\n## {title}\n")
             for k in sorted(ks):
                 print(f"- `{k[1]}` ({k[0]}): {row(old[k])} -> {row(new.get(k, {}))}")
+    if plain:
+        return
     worse = []
     print("\n## The EXT instantiations against the policy instantiation they are a variant of\n")
     print("(POL sibling -> EXT)\n")
