@@ -176,6 +176,15 @@ void orc_poisson_fill(uint64_t rng[4], double lam, int64_t *out, int64_t n) {
  * random/src/distributions/distributions.c + pcg64.h), the demand samplers of
  * inventory_management.py:173-182 (dist 2, 3, 4). */
 
+/* Branch counters (orc_dist_fill_counted, oracle.h ORC_C_*): every sampler
+ * below takes `cnt`, the caller's own array or NULL for no counting, down as
+ * an argument; nothing here is shared between callers, so the env loops
+ * (which pass NULL through the orc_* entry points) stay free of shared state. */
+#define CNT(i)              \
+    do {                    \
+        if (cnt) cnt[i]++;  \
+    } while (0)
+
 /* pcg64_next32: the low half of a 64-bit output first, the high half buffered
  * in the bit generator (has_uint32 / uinteger) for the next 32-bit draw */
 uint32_t orc_next32(uint64_t rng[4], uint32_t *buf /* [2]: has, value */) {
@@ -191,16 +200,24 @@ uint32_t orc_next32(uint64_t rng[4], uint32_t *buf /* [2]: has, value */) {
 
 /* random_bounded_uint64_fill(cnt = 1, use_masked = false): off + [0, rng] via
  * Lemire's method (32-bit buffered draws when rng fits in 32 bits) */
-uint64_t orc_bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64_t r) {
-    if (r == 0) return off;
+static uint64_t bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64_t r, int64_t *cnt) {
+    if (r == 0) {
+        CNT(ORC_C_INT_CONST);
+        return off;
+    }
     if (r <= 0xFFFFFFFFULL) {
-        if (r == 0xFFFFFFFFULL) return off + orc_next32(rng, buf);
+        if (r == 0xFFFFFFFFULL) {
+            CNT(ORC_C_INT_FULL32);
+            return off + orc_next32(rng, buf);
+        }
+        CNT(ORC_C_INT32_DRAW);
         const uint32_t rng_excl = (uint32_t)r + 1;
         uint64_t m = (uint64_t)orc_next32(rng, buf) * rng_excl;
         uint32_t leftover = (uint32_t)m;
         if (leftover < rng_excl) {
             const uint32_t threshold = (uint32_t)((UINT32_MAX - (uint32_t)r) % rng_excl);
             while (leftover < threshold) {
+                CNT(ORC_C_INT32_REJECT);
                 m = (uint64_t)orc_next32(rng, buf) * rng_excl;
                 leftover = (uint32_t)m;
             }
@@ -208,12 +225,14 @@ uint64_t orc_bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64
         return off + (m >> 32);
     }
     if (r == 0xFFFFFFFFFFFFFFFFULL) return off + orc_next64(rng);
+    CNT(ORC_C_INT64_DRAW);
     const uint64_t rng_excl = r + 1;
     u128 m = (u128)orc_next64(rng) * rng_excl;
     uint64_t leftover = (uint64_t)m;
     if (leftover < rng_excl) {
         const uint64_t threshold = (UINT64_MAX - r) % rng_excl;
         while (leftover < threshold) {
+            CNT(ORC_C_INT64_REJECT);
             m = (u128)orc_next64(rng) * rng_excl;
             leftover = (uint64_t)m;
         }
@@ -221,14 +240,22 @@ uint64_t orc_bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64
     return off + (uint64_t)(m >> 64);
 }
 
+uint64_t orc_bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64_t r) {
+    return bounded_uint64(rng, buf, off, r, NULL);
+}
+
 /* Generator.integers(low, high) (high exclusive, int64) */
-int64_t orc_integers(uint64_t rng[4], uint32_t *buf, int64_t low, int64_t high) {
+static int64_t integers_c(uint64_t rng[4], uint32_t *buf, int64_t low, int64_t high, int64_t *cnt) {
     const uint64_t r = (uint64_t)high - (uint64_t)low - 1;
-    return (int64_t)orc_bounded_uint64(rng, buf, (uint64_t)low, r);
+    return (int64_t)bounded_uint64(rng, buf, (uint64_t)low, r, cnt);
+}
+
+int64_t orc_integers(uint64_t rng[4], uint32_t *buf, int64_t low, int64_t high) {
+    return integers_c(rng, buf, low, high, NULL);
 }
 
 /* random_binomial_inversion (n * p <= 30) */
-static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p) {
+static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
     const double q = 1.0 - p;
     const double qn = exp(n * log(q));
     const double np = n * p;
@@ -236,9 +263,11 @@ static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p) {
     int64_t X = 0;
     double px = qn;
     double U = orc_next_double(rng);
+    CNT(ORC_C_BINOM_INVERSION);
     while (U > px) {
         X++;
         if (X > bound) {
+            CNT(ORC_C_INV_RESTART);
             X = 0;
             px = qn;
             U = orc_next_double(rng);
@@ -251,7 +280,7 @@ static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p) {
 }
 
 /* random_binomial_btpe (n * p > 30, p <= 0.5) */
-static int64_t binomial_btpe(uint64_t rng[4], int64_t n, double p) {
+static int64_t binomial_btpe(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
     const double r = fmin(p, 1.0 - p);
     const double q = 1.0 - r;
     const double fm = n * r + r;
@@ -275,10 +304,12 @@ step10:
     u = orc_next_double(rng) * p4;
     v = orc_next_double(rng);
     if (u > p1) goto step20;
+    CNT(ORC_C_BTPE_TRIANGLE);
     y = (int64_t)floor(xm - p1 * v + u);
     goto step60;
 step20:
     if (u > p2) goto step30;
+    CNT(ORC_C_BTPE_PARALLELOGRAM);
     x = xl + (u - p1) / c;
     v = v * c + 1.0 - fabs(m - x + 0.5) / p1;
     if (v > 1.0) goto step10;
@@ -286,17 +317,20 @@ step20:
     goto step50;
 step30:
     if (u > p3) goto step40;
+    CNT(ORC_C_BTPE_LEFT_TAIL);
     y = (int64_t)floor(xl + log(v) / laml);
     if ((y < 0) || (v == 0.0)) goto step10;
     v = v * (u - p2) * laml;
     goto step50;
 step40:
+    CNT(ORC_C_BTPE_RIGHT_TAIL);
     y = (int64_t)floor(xr - log(v) / lamr);
     if ((y > n) || (v == 0.0)) goto step10;
     v = v * (u - p3) * lamr;
 step50:
     k = llabs(y - m);
     if ((k > 20) && (k < ((nrq) / 2.0 - 1))) goto step52;
+    CNT(ORC_C_BTPE_FPRODUCT);
     s = r / q;
     a = s * (n + 1);
     F = 1.0;
@@ -305,14 +339,25 @@ step50:
     } else if (m > y) {
         for (i = y + 1; i <= m; i++) F /= (a / i - s);
     }
-    if (v > F) goto step10;
+    if (v > F) {
+        CNT(ORC_C_BTPE_FPRODUCT_REJECT);
+        goto step10;
+    }
     goto step60;
 step52:
+    CNT(ORC_C_BTPE_STEP52);
     rho = (k / (nrq)) * ((k * (k / 3.0 + 0.625) + 0.16666666666666666) / nrq + 0.5);
     t = -k * k / (2 * nrq);
     A = log(v);
-    if (A < (t - rho)) goto step60;
-    if (A > (t + rho)) goto step10;
+    if (A < (t - rho)) {
+        CNT(ORC_C_BTPE_QUICK_ACCEPT);
+        goto step60;
+    }
+    if (A > (t + rho)) {
+        CNT(ORC_C_BTPE_QUICK_REJECT);
+        goto step10;
+    }
+    CNT(ORC_C_BTPE_FOUR_LOG);
     x1 = y + 1;
     f1 = m + 1;
     z = n + 1 - m;
@@ -325,24 +370,32 @@ step52:
              (13680. - (462. - (132. - (99. - 140. / f2) / f2) / f2) / f2) / f1 / 166320. +
              (13680. - (462. - (132. - (99. - 140. / z2) / z2) / z2) / z2) / z / 166320. +
              (13680. - (462. - (132. - (99. - 140. / x2) / x2) / x2) / x2) / x1 / 166320. +
-             (13680. - (462. - (132. - (99. - 140. / w2) / w2) / w2) / w2) / w / 166320.))
+             (13680. - (462. - (132. - (99. - 140. / w2) / w2) / w2) / w2) / w / 166320.)) {
+        CNT(ORC_C_BTPE_FOUR_LOG_REJECT);
         goto step10;
+    }
 step60:
     if (p > 0.5) y = n - y;
     return y;
 }
 
 /* random_binomial */
-int64_t orc_binomial(uint64_t rng[4], int64_t n, double p) {
-    if ((n == 0) || (p == 0.0f)) return 0;
-    if (p <= 0.5) {
-        if (p * n <= 30.0) return binomial_inversion(rng, n, p);
-        return binomial_btpe(rng, n, p);
+static int64_t binomial_c(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
+    if ((n == 0) || (p == 0.0f)) {
+        CNT(ORC_C_BINOM_ZERO);
+        return 0;
     }
+    if (p <= 0.5) {
+        if (p * n <= 30.0) return binomial_inversion(rng, n, p, cnt);
+        return binomial_btpe(rng, n, p, cnt);
+    }
+    CNT(ORC_C_BINOM_FLIP);
     const double q = 1.0 - p;
-    if (q * n <= 30.0) return n - binomial_inversion(rng, n, q);
-    return n - binomial_btpe(rng, n, q);
+    if (q * n <= 30.0) return n - binomial_inversion(rng, n, q, cnt);
+    return n - binomial_btpe(rng, n, q, cnt);
 }
+
+int64_t orc_binomial(uint64_t rng[4], int64_t n, double p) { return binomial_c(rng, n, p, NULL); }
 
 #include "numpy_ziggurat.h"
 #ifdef _OPENMP
@@ -363,7 +416,7 @@ int orc_max_threads(void) {
 }
 
 /* random_standard_exponential (256-level ziggurat, tables from numpy) */
-double orc_standard_exponential(uint64_t rng[4]) {
+static double standard_exponential_c(uint64_t rng[4], int64_t *cnt) {
     for (;;) {
         uint64_t ri = orc_next64(rng);
         ri >>= 3;
@@ -371,38 +424,62 @@ double orc_standard_exponential(uint64_t rng[4]) {
         ri >>= 8;
         const double x = ri * npz_we[idx];
         if (ri < npz_ke[idx]) return x;
-        if (idx == 0) return NPZ_EXP_R - log1p(-orc_next_double(rng));
-        if ((npz_fe[idx - 1] - npz_fe[idx]) * orc_next_double(rng) + npz_fe[idx] < exp(-x)) return x;
+        CNT(ORC_C_ZIG_SLOW);
+        if (idx == 0) {
+            CNT(ORC_C_ZIG_TAIL);
+            return NPZ_EXP_R - log1p(-orc_next_double(rng));
+        }
+        if ((npz_fe[idx - 1] - npz_fe[idx]) * orc_next_double(rng) + npz_fe[idx] < exp(-x)) {
+            CNT(ORC_C_ZIG_WEDGE_ACCEPT);
+            return x;
+        }
+        CNT(ORC_C_ZIG_WEDGE_REJECT);
     }
 }
 
+double orc_standard_exponential(uint64_t rng[4]) { return standard_exponential_c(rng, NULL); }
+
 /* random_geometric: search for p >= 1/3, else inversion of the exponential */
-int64_t orc_geometric(uint64_t rng[4], double p) {
+static int64_t geometric_c(uint64_t rng[4], double p, int64_t *cnt) {
     if (p >= 0.333333333333333333333333) {
         int64_t X = 1;
         double sum = p, prod = p;
         const double q = 1.0 - p;
         const double U = orc_next_double(rng);
         while (U > sum) {
+            CNT(ORC_C_GEOM_SEARCH);
             prod *= q;
             sum += prod;
             X++;
         }
         return X;
     }
-    const double z = ceil(-orc_standard_exponential(rng) / log1p(-p));
-    if (z >= 9.223372036854776e+18) return INT64_MAX;
+    CNT(ORC_C_GEOM_INVERSION);
+    const double z = ceil(-standard_exponential_c(rng, cnt) / log1p(-p));
+    if (z >= 9.223372036854776e+18) {
+        CNT(ORC_C_GEOM_CLAMP);
+        return INT64_MAX;
+    }
     return (int64_t)z;
+}
+
+int64_t orc_geometric(uint64_t rng[4], double p) { return geometric_c(rng, p, NULL); }
+
+/* counts: NULL, or the caller's own int64[ORC_NCOUNT] that the draws add to */
+void orc_dist_fill_counted(uint64_t rng[4], uint32_t *buf, int dist, int64_t n_or_low, int64_t high, double p,
+                           int64_t *out, int64_t count, int64_t *counts) {
+    int64_t *const cnt = counts;
+    for (int64_t i = 0; i < count; i++) {
+        if (dist == 2) out[i] = binomial_c(rng, n_or_low, p, cnt);
+        else if (dist == 3) out[i] = integers_c(rng, buf, n_or_low, high, cnt);
+        else if (dist == 4) out[i] = geometric_c(rng, p, cnt);
+        else out[i] = 0;
+    }
 }
 
 void orc_dist_fill(uint64_t rng[4], uint32_t *buf, int dist, int64_t n_or_low, int64_t high, double p,
                    int64_t *out, int64_t count) {
-    for (int64_t i = 0; i < count; i++) {
-        if (dist == 2) out[i] = orc_binomial(rng, n_or_low, p);
-        else if (dist == 3) out[i] = orc_integers(rng, buf, n_or_low, high);
-        else if (dist == 4) out[i] = orc_geometric(rng, p);
-        else out[i] = 0;
-    }
+    orc_dist_fill_counted(rng, buf, dist, n_or_low, high, p, out, count, NULL);
 }
 
 double orc_exponential_fill(uint64_t rng[4], double *out, int64_t count) {

@@ -44,6 +44,7 @@ def _lib():
     lib.orc_poisson.restype = C.c_int64
     lib.orc_poisson_fill.argtypes = [P, C.c_double, P, C.c_int64]
     lib.orc_dist_fill.argtypes = [P, P, C.c_int, C.c_int64, C.c_int64, C.c_double, P, C.c_int64]
+    lib.orc_dist_fill_counted.argtypes = [P, P, C.c_int, C.c_int64, C.c_int64, C.c_double, P, C.c_int64, P]
     lib.orc_exponential_fill.argtypes = [P, P, C.c_int64]
     lib.orc_exponential_fill.restype = C.c_double
     lib.orc_loggam.argtypes = [C.c_double]
@@ -136,6 +137,29 @@ def dist_stream(seed, dist, n, n_or_low=0, high=0, p=0.0):
     out = np.zeros(n, np.int64)
     lib().orc_dist_fill(_p(st), _p(buf), int(dist), int(n_or_low), int(high), float(p), _p(out), n)
     return out, st, buf
+
+
+# oracle.h ORC_C_*: the index of each branch counter
+COUNTERS = ("int_const", "int_full32", "int32_draw", "int32_reject", "int64_draw", "int64_reject",
+            "binom_zero", "binom_flip", "binom_inversion", "inv_restart",
+            "btpe_triangle", "btpe_parallelogram", "btpe_left_tail", "btpe_right_tail",
+            "btpe_fproduct", "btpe_fproduct_reject", "btpe_step52", "btpe_quick_accept",
+            "btpe_quick_reject", "btpe_four_log", "btpe_four_log_reject",
+            "geom_search", "geom_inversion", "geom_clamp",
+            "zig_slow", "zig_tail", "zig_wedge_accept", "zig_wedge_reject")
+
+
+def dist_stream_counts(seed, dist, n, n_or_low=0, high=0, p=0.0, state=None, buf=None):
+    """dist_stream plus the branches the draws took: (draws, state, buf,
+    {counter name: events}).  `state` / `buf` (as returned) continue a stream
+    instead of seeding one; they are updated in place."""
+    st = pcg64_init(seed) if state is None else state
+    buf = np.zeros(2, np.uint32) if buf is None else buf
+    out = np.zeros(n, np.int64)
+    cnt = np.zeros(len(COUNTERS), np.int64)
+    lib().orc_dist_fill_counted(_p(st), _p(buf), int(dist), int(n_or_low), int(high), float(p), _p(out), n,
+                                _p(cnt))
+    return out, st, buf, dict(zip(COUNTERS, cnt.tolist()))
 
 
 def exponential_stream(seed, n):

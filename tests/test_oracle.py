@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import numpy_sampler_cases as cases
 from conftest import IM_GOLDENS, NET_GOLDENS, NV_GOLDENS, im_kwargs, load_golden, nv_kwargs
 
 
@@ -170,27 +171,129 @@ def test_standard_exponential_vs_numpy(oracle, seed):
     assert np.array_equal(a.view(np.uint64), _npg(seed).standard_exponential(100000).view(np.uint64))
 
 
+def _same_generator(st, buf, g):
+    """the oracle's PCG64 state (and, for integers, its buffered 32-bit half) is numpy's bit generator's"""
+    d = g.bit_generator.state
+    m = 2**64 - 1
+    assert [int(x) for x in st] == [d["state"]["state"] >> 64, d["state"]["state"] & m,
+                                    d["state"]["inc"] >> 64, d["state"]["inc"] & m]
+    if buf is not None:
+        assert (int(buf[0]), int(buf[1])) == (d["has_uint32"], d["uinteger"])
+
+
+# (low, high exclusive).  Powers of two have threshold 0 and most other ranges reject with probability
+# <= 2^-32, so the Lemire rejection loops run only on the ranges of the second line: 2^31 + 1 and
+# 3 * 2^30 + 1 (32-bit loop, probability 1/2 and ~1/4), 2^57 + 1 and 2^63 + 1 (64-bit loop, 2^-7 and 1/2).
+# The third line: rng == 0 (no draw), rng == 0xFFFFFFFF (a raw 32-bit draw), the widest int64 range,
+# and rng + 1 == 2^31, where every even draw has leftover == threshold == 0 (accepted).
 @pytest.mark.parametrize("lo,hi", [(0, 11), (5, 300), (-50, 50), (0, 2**32), (0, 2**32 + 1), (0, 2**40),
-                                   (-2**62, 2**62), (3, 4)])
+                                   (-2**62, 2**62), (3, 4), (0, 41), (-5, 2**40 + 1),
+                                   (0, 2**31 + 1), (0, 3 * 2**30 + 1), (0, 2**57 + 1), (-2**62, 2**62 + 1),
+                                   (5, 6), (7, 8), (0, 2**32 - 1), (-3, 2**63 - 1), (0, 2**31)])
 def test_integers_vs_numpy(oracle, lo, hi):
-    a, _, _ = oracle.dist_stream(3, 3, 20001, lo, hi)
+    a, st, buf = oracle.dist_stream(3, 3, 20001, lo, hi)
     g = _npg(3)
     assert np.array_equal(a, np.array([g.integers(lo, hi) for _ in range(20001)]))
+    _same_generator(st, buf, g)
 
 
 @pytest.mark.parametrize("n,p", [(10, 0.5), (100, 0.2), (100, 0.35), (1000, 0.5), (20, 0.9), (1000, 0.97),
-                                 (50, 0.01), (5000, 0.3), (7, 1.0), (0, 0.3), (40, 0.0)])
+                                 (50, 0.01), (5000, 0.3), (7, 1.0), (0, 0.3), (40, 0.0),
+                                 (1000, 0.3), (300, 0.8), (400, 0.05), (100000, 0.5)])
 def test_binomial_vs_numpy(oracle, n, p):
-    a, _, _ = oracle.dist_stream(11, 2, 20000, n, 0, p)
+    a, st, _ = oracle.dist_stream(11, 2, 20000, n, 0, p)
     g = _npg(11)
     assert np.array_equal(a, np.array([g.binomial(n, p) for _ in range(20000)]))
+    _same_generator(st, None, g)
 
 
-@pytest.mark.parametrize("p", [1.0, 0.5, 0.34, 1 / 3, 0.3333333333333333, 0.2, 0.05, 0.001, 1e-9])
+@pytest.mark.parametrize("p", [1.0, 0.5, 0.34, 1 / 3, 0.3333333333333333, float(np.nextafter(1 / 3, 0)), 0.2, 0.05,
+                               0.001, 1e-4, 1e-9, 1e-300])
 def test_geometric_vs_numpy(oracle, p):
-    a, _, _ = oracle.dist_stream(5, 4, 20000, 0, 0, p)
+    a, st, _ = oracle.dist_stream(5, 4, 20000, 0, 0, p)
     g = _npg(5)
     assert np.array_equal(a, np.array([g.geometric(p) for _ in range(20000)]))
+    _same_generator(st, None, g)
+    if p == 1e-300:
+        assert (a == 2**63 - 1).all()                  # the clamp, every draw
+
+
+def test_no_draw_parameters_in_numpy_itself():
+    """What the GPU cases marked no_draw rest on, from numpy directly:
+    integers(7, 8), binomial(0, p) and binomial(n, 0.0) return without touching
+    the bit generator; binomial(7, 1.0) does NOT (it flips to q = 0 and draws
+    the inversion's one uniform), though it always returns 7."""
+    for c in cases.CASES:
+        if not (c.get("no_draw") or "constant" in c):
+            continue
+        g = _npg(cases.BASE_SEED)
+        before = g.bit_generator.state
+        lo, hi, p = cases.oracle_args(c)
+        fn = {2: lambda: g.binomial(lo, p), 3: lambda: g.integers(lo, hi), 4: lambda: g.geometric(p)}[c["dist"]]
+        vals = {int(fn()) for _ in range(50)}
+        if "constant" in c:
+            assert vals == {c["constant"]}, c["id"]
+        assert (g.bit_generator.state == before) == bool(c.get("no_draw")), c["id"]
+
+
+# ---------------------------------------------------------------- branch counters and the GPU cases' coverage
+@pytest.mark.parametrize("case", cases.CASES, ids=cases.CASE_IDS)
+def test_counted_fill_equals_uncounted(oracle, case):
+    """orc_dist_fill_counted draws what orc_dist_fill draws: values, generator
+    state and buffered half, also when a stream is continued in pieces."""
+    lo, hi, p = cases.oracle_args(case)
+    for seed in (cases.BASE_SEED, cases.BASE_SEED + 999, 2**70 + 3):
+        a, st, buf = oracle.dist_stream(seed, case["dist"], 300, lo, hi, p)
+        b, st2, buf2, cnt = oracle.dist_stream_counts(seed, case["dist"], 300, lo, hi, p)
+        assert np.array_equal(a, b) and np.array_equal(st, st2) and np.array_equal(buf, buf2)
+        assert set(cnt) == set(oracle.COUNTERS) and all(v >= 0 for v in cnt.values())
+        c1, st3, buf3, _ = oracle.dist_stream_counts(seed, case["dist"], 101, lo, hi, p)
+        c2, st3, buf3, _ = oracle.dist_stream_counts(seed, case["dist"], 199, lo, hi, p, state=st3, buf=buf3)
+        assert np.array_equal(np.concatenate([c1, c2]), a) and np.array_equal(st3, st) and np.array_equal(buf3, buf)
+        assert cnt["zig_slow"] == cnt["zig_tail"] + cnt["zig_wedge_accept"] + cnt["zig_wedge_reject"]
+        assert cnt["btpe_step52"] == cnt["btpe_quick_accept"] + cnt["btpe_quick_reject"] + cnt["btpe_four_log"]
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=cases.CASE_IDS)
+def test_gpu_sampler_cases_reach_their_branches(oracle, case):
+    """Over exactly the streams tests/test_gpu_numpy_samplers.py compares on the
+    device (seeds BASE_SEED .. BASE_SEED + N_ENV - 1, the phases' draw counts),
+    every branch the case targets is taken at least FLOOR times, and the
+    branches it is there to avoid are not taken at all."""
+    s = cases.streams(case["id"])
+    cnt = s["counts"]
+    print(case["id"], s["marks"][-1], "draws/env:", {k: v for k, v in cnt.items() if v})
+    for name in case["targets"]:
+        assert cnt[name] >= cases.FLOOR, (case["id"], name, cnt[name])
+    for name in case["never"]:
+        assert cnt[name] == 0, (case["id"], name, cnt[name])
+    # the inversion's restart needs X > np + 10 sqrt(npq + 1), about 10 sigma out:
+    # 0 is the expected count on any feasible number of draws, and no case targets it
+    assert cnt["inv_restart"] == 0
+    d = s["draws"]
+    if "constant" in case:
+        assert (d == case["constant"]).all()
+    if case.get("no_draw"):                    # the generator never moves: every mark holds the seeded state
+        assert (s["states"] == s["states"][:1]).all() and (s["bufs"] == 0).all()
+    if "int32_reject" in case["targets"]:      # a rejected draw shifts the buffered half: both parities are live
+        assert 0 < (s["bufs"] != 0).sum() < s["bufs"].size
+
+
+@pytest.mark.parametrize("id,dist,dp", cases.FAST_CASES, ids=[c[0] for c in cases.FAST_CASES])
+def test_chi_square_check_passes_numpys_own_samplers(id, dist, dp):
+    """The fast stream's GPU check (chi2_pmf against the exact pmf, p > P_MIN on
+    FAST_ENVS x FAST_DRAWS draws) is one the reference sampler itself stays
+    within: numpy's own draws, as many, at a fixed seed."""
+    pytest.importorskip("scipy")
+    g = np.random.Generator(np.random.PCG64(2024))
+    n = cases.FAST_ENVS * cases.FAST_DRAWS
+    x = {2: lambda: g.binomial(dp["n"], dp["p"], n), 3: lambda: g.integers(dp["low"], dp["high"] + 1, n),
+         4: lambda: g.geometric(dp["p"], n)}[dist]()
+    kmax = cases.fast_kmax(dist, dp)
+    counts = np.bincount(np.minimum(x, kmax), minlength=kmax + 1)
+    stat, dof, p = cases.chi2_pmf(counts, cases.exact_pmf(dist, dp, kmax))
+    print(id, f"chi-square {stat:.1f} on {dof} dof, p = {p:.3g}")
+    assert dof >= 30 and p > cases.P_MIN
 
 
 @pytest.mark.parametrize("dist,dp", [(2, {"n": 40, "p": 0.5}), (2, {"n": 400, "p": 0.05}),
