@@ -211,6 +211,9 @@ int invsim_status(invsim_handle *h, uint32_t *flags, int32_t clear);
  *   INVSIM_POLICY_RANDOM       RandomAgent (env.action_space.sample() every step; the first
  *                              agent of every benchmark_*.py list), any family and any graph:
  *                              see "RandomAgent" below
+ *   INVSIM_POLICY_LEVELS       BaseStockAgent's rule with per-env, per-stage order-up-to levels
+ *                              (and optional reorder points) from attached device arrays
+ *                              (InvMgmt): see "Per-env base-stock levels" below
  * CLASSIC_NV / SS need mu_max * (lead_time + 1) * max(1, safety_factor) <= 1e6 (INVSIM_ERANGE).
  * Per-env metrics (f64, accumulated with += so a caller may chain launches),
  * the sums evaluate_agent keeps (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -414,6 +417,46 @@ int invsim_seed_action_rng(invsim_handle *h, uint64_t *arng, uint64_t base_lo, u
 int invsim_set_action_rng(invsim_handle *h, uint64_t *arng);
 int invsim_sample_actions(invsim_handle *h, int32_t K, const void *high, void *actions /* [K][N][A] */,
                           void *stream);
+
+/* ---- Per-env base-stock levels (INVSIM_POLICY_LEVELS; InvMgmt handles only).
+ * The reference's BaseStockAgent orders up to (L_i + 1) * mu * safety_factor,
+ * one scalar for every stage and env, and calls that "a HUGE simplification"
+ * (benchmark_InvManagementBacklogEnv.py:145-148).  LEVELS is the same rule with
+ * the order-up-to level of every env and stage read from a device array, so
+ * one launch scores N candidate level vectors (under common random numbers
+ * when the envs are seeded alike).
+ *
+ * invsim_set_policy_levels attaches `levels`, and optionally `reorder`, to h:
+ * device f64 [N][action_dim], caller-owned, not copied, read by every LEVELS
+ * launch at the time it runs: the caller may rewrite them on the same stream
+ * between launches, and a captured graph reads the current values at every
+ * replay.  NULL levels detaches both.  Not during capture, and not on another
+ * family's handle (INVSIM_EINVAL).
+ *
+ * invsim_rollout_policy with kind = INVSIM_POLICY_LEVELS (safety_factor, mu,
+ * variant and constant are ignored; INVSIM_EINVAL on another family's handle or
+ * with nothing attached).  For env n, stage i, at an applied step of period t,
+ * bit for bit:
+ *   pos = I[t][i] + sum(action_log[max(0, t - L_i) : t, i])   int64, wrapping,
+ *                                                  as BASE_STOCK sums it
+ *   x = levels[n][i] - (double)pos
+ *   with reorder: if not ((double)pos < reorder[n][i]) then x = 0   (the strict <
+ *                 of the reference's sSPolicyAgent; a NaN reorder point never orders)
+ *   x = x > 0 ? x : 0                              (a NaN level orders 0)
+ *   x = x > (double)c_i ? (double)c_i : x
+ *   action = (int64_t)x
+ * With reorder == NULL and levels[n][i] the f64 value of ((double)(L_i + 1) * mu)
+ * * sf, the launch is bit-identical to INVSIM_POLICY_BASE_STOCK with that mu and
+ * sf: actions, obs, rewards, flags, metrics, the state blob and the RNG state.
+ * Everything else is BASE_STOCK's: `actions` records the order of every stepped
+ * env, a NEXT_STEP reset step leaves its row unwritten and adds nothing to the
+ * metrics (same columns, same += order), SAME_STEP is refused, and the horizon
+ * refusal, the episode sink, the capture bracket, both demand streams, every
+ * `dist`, lock-step and per-env periods are unchanged.  It runs on the launch
+ * paths BASE_STOCK has (the fused rollout kernels of the default lead times,
+ * the one-wave run kernel otherwise). */
+#define INVSIM_POLICY_LEVELS 7
+int invsim_set_policy_levels(invsim_handle *h, const double *levels, const double *reorder);
 
 /* Episodic-return statistics of K steps of outputs, the reduction the
  * reference's evaluation harness keeps per episode (episode_rewards ->

@@ -84,6 +84,8 @@ struct invsim_handle {
     int64_t cap_steps = 0;
     // RandomAgent's action generators (invsim_set_action_rng): caller-owned u64 [4][Npad], or null
     uint64_t *arng = nullptr;
+    // the LEVELS policy's per-env parameters (invsim_set_policy_levels): caller-owned f64 [N][action_dim], or null
+    const double *levels = nullptr, *reorder = nullptr;
     std::string err;
 };
 
@@ -1203,6 +1205,15 @@ int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *poli
         case INVSIM_POLICY_RANDOM:
             if (int rc = random_policy(h, policy->constant, p, true)) return rc;
             break;
+        case INVSIM_POLICY_LEVELS:
+            if (h->family != INVSIM_INVMGMT) return fail(h, INVSIM_EINVAL, "LEVELS is an InvMgmt policy");
+            if (!h->levels)
+                return fail(h, INVSIM_EINVAL, "no levels attached: attach a device f64 [N][action_dim] array with "
+                                              "invsim_set_policy_levels");
+            p.kind = POL_LEVELS;        // (the public 7 is POL_EXTERNAL inside)
+            p.levels = h->levels;       // safety_factor / mu are ignored: their slots hold the two pointers
+            p.reorder = h->reorder;
+            break;
         default: return fail(h, INVSIM_EINVAL, "unknown policy kind");
     }
     DeviceGuard g(h->device);
@@ -1434,6 +1445,15 @@ int invsim_set_action_rng(invsim_handle *h, uint64_t *arng) {
     if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
     if (int rc = refuse_in_capture(h, "set_action_rng")) return rc;
     h->arng = arng;
+    return INVSIM_OK;
+}
+
+int invsim_set_policy_levels(invsim_handle *h, const double *levels, const double *reorder) {
+    if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
+    if (int rc = refuse_in_capture(h, "set_policy_levels")) return rc;
+    if (h->family != INVSIM_INVMGMT) return fail(h, INVSIM_EINVAL, "LEVELS is an InvMgmt policy");
+    h->levels = levels;
+    h->reorder = levels ? reorder : nullptr;
     return INVSIM_OK;
 }
 

@@ -52,6 +52,17 @@
 #else
 #define IM_EXT 0
 #endif
+// invmgmt_lvl.hip compiles this file with INVSIM_IM_LVL_TU: every policy kernel
+// instantiated there is the LEVELS variant, BaseStock's inventory position
+// against the env's own order-up-to levels (and optional reorder points) from
+// the attached device arrays instead of one (L + 1) * mu * sf target.  As for
+// RANDOM the variant is a translation unit, so the other objects' kernels pay
+// neither the per-env loads nor their registers.
+#ifdef INVSIM_IM_LVL_TU
+#define IM_LVL 1
+#else
+#define IM_LVL 0
+#endif
 
 namespace invsim {
 namespace {
@@ -220,6 +231,40 @@ __device__ __forceinline__ int64_t im_base_stock_order(const PolicyIO &pol, int 
     x = (x > (double)c) ? (double)c : x;
     return (int64_t)x;                                              // astype(int64)
 }
+
+#if IM_LVL
+// INVSIM_POLICY_LEVELS for one stage (invsim.h): order up to the env's level lv
+// over the inventory position pos, only while pos is below the reorder point ro
+// (the strict < of the reference's sSPolicyAgent; +inf without reorder points,
+// which every (double)pos is below), clipped to [0, c] and truncated as
+// im_base_stock_order.  A NaN level or reorder point orders 0.
+__device__ __forceinline__ int64_t im_levels_order(double lv, double ro, int64_t pos, int64_t c) {
+    double x = lv - (double)pos;
+    x = ((double)pos < ro) ? x : 0.0;
+    x = (x > 0) ? x : 0.0;
+    x = (x > (double)c) ? (double)c : x;
+    return (int64_t)x;
+}
+
+// An env's row of the attached arrays (row: the env, clamped to N - 1 by the
+// caller: the arrays are [N][M1], not padded)
+template <int M1>
+struct ImLevels {
+    double lv[M1], ro[M1];
+    __device__ __forceinline__ void load(const PolicyIO &pol, int64_t row) {
+#pragma unroll
+        for (int i = 0; i < M1; i++) lv[i] = pol.levels[row * M1 + i];
+#pragma unroll
+        for (int i = 0; i < M1; i++) ro[i] = pol.reorder ? pol.reorder[row * M1 + i] : __builtin_huge_val();
+    }
+};
+// Where the row lives in the fused rollout kernels follows the compiler's
+// resource report: im_roll3o_kernel's dynamics wave has the registers to keep
+// it over the launch's K steps (200 VGPRs at most, no scratch); im_roll3_kernel,
+// at its 256-VGPR cap (waves_per_eu(2)), would spill 4 VGPRs (20 B of scratch)
+// to hold it, so it reads the row again at the top of every step (cache
+// resident after the first) and is back at 254 VGPRs without scratch.
+#endif
 
 // The PTRS right-hand-side table (or, without one, any valid words) into a
 // TableStage bound for dst in LDS: a fixed count of clamped loads, issued in
@@ -475,6 +520,10 @@ __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO 
                                               int t, int64_t e, int64_t (&act)[M1]) {
     const int64_t S = P.cm.Npad;
     const int D = P.lt_max;
+#if IM_LVL
+    ImLevels<M1> lvl;                                               // (lanes past N: the last env's row)
+    lvl.load(pol, e < P.cm.N ? e : P.cm.N - 1);
+#endif
 #pragma unroll
     for (int i = 0; i < M1; i++) {
         const int L = P.L[i];
@@ -488,7 +537,11 @@ __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO 
             }
             pos = wrap_add(pos, pipe);
         }
+#if IM_LVL
+        act[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+#else
         act[i] = im_base_stock_order(pol, L, pos, P.c[i]);
+#endif
     }
 }
 
@@ -554,7 +607,7 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
         // the caller's row, as without a policy
 #else
         if (POL) {
-            if (pol.kind == POL_BASE_STOCK) {
+            if (IM_LVL || pol.kind == POL_BASE_STOCK) {
                 im_base_stock<M1, BACKLOG>(P, pol, st, t, e, pact);
             } else {
 #pragma unroll
@@ -1443,6 +1496,10 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                 const int tn = (t >= P.periods) ? 0 : t + 1;     // the next launch step's period
                 napow = P.alpha_pow[tn < P.periods ? tn : 0];
             }
+#if IM_LVL
+            ImLevels<M1> lvl;                      // read again every step (see ImLevels)
+            lvl.load(pol, el);
+#endif
             if (!POL && k + 1 < K) {               // prefetch the next step's actions
 #pragma unroll
                 for (int i = 0; i < M1; i++) nact[i] = io.act[((int64_t)(k + 1) * N + el) * M1 + i];
@@ -1464,7 +1521,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
             } else {
                 const int64_t d = db[kk * WAVE + lane];
                 if (POL && !IM_RND) {
-                    if (pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register windows
+                    if (IM_LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register windows
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
                             constexpr int DD = D;
@@ -1476,7 +1533,11 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                                 if (t - a >= 0) pipe = wrap_add(pipe, v);
                             }
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
+#if IM_LVL
+                            req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+#else
                             req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
+#endif
                         }
                     } else {
 #pragma unroll
@@ -1825,6 +1886,10 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     ActGen ag;
     ag.load(pol, S, el);
 #endif
+#if IM_LVL
+    ImLevels<M1> lvl;                              // held over the K steps
+    lvl.load(pol, el);
+#endif
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
     // the group's partials are read only after the loop (they would hold 8
     // VGPRs through it: the policy kernel then needs AGPRs, one wave per SIMD)
@@ -1873,7 +1938,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
             } else {
                 const int64_t d = db[kk * WAVE + lane];
                 if (POL && !IM_RND) {
-                    if (pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register history
+                    if (IM_LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register history
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
                             int64_t pos = I[i];                                 // observation[:M1] = I[t]
@@ -1882,7 +1947,11 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                             for (int a = 0; a < G::lt(i); a++)                  // action_log[max(0, t - L_i) : t, i]
                                 if (t - 1 - a >= 0) pipe = wrap_add(pipe, hv[i][a]);
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
+#if IM_LVL
+                            req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+#else
                             req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
+#endif
                         }
                     } else {
 #pragma unroll
@@ -2013,7 +2082,8 @@ inline bool im_sink_noop(const ImParams &p, int t_u, const PolicyIO *pol, const 
 // (open loop, or the in-kernel BaseStock / ConstantOrder agents)
 inline bool im_roll_applies(const ImParams &p, int M1, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io) {
-    const bool pol_roll = pol && (pol->kind == POL_BASE_STOCK || pol->kind == POL_CONSTANT || pol->kind == POL_RANDOM) &&
+    const bool pol_roll = pol && (pol->kind == POL_BASE_STOCK || pol->kind == POL_CONSTANT || pol->kind == POL_RANDOM ||
+                                  pol->kind == POL_LEVELS) &&
                           p.cm.kn.im_pol_roll;
     return (!pol || pol_roll) && io.K > 1 && t_u >= 0 && p.cm.autoreset != AR_SAME_STEP && p.dist == 1 &&
            !p.cm.info_rec && M1 == 3 && p.L[0] == 1 && p.L[1] == 5 && p.L[2] == 10 && p.lt_max == 10 &&
@@ -2060,7 +2130,7 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
         if (backlog) R_(true, true);
         else R_(false, true);
     } else {
-#if !IM_RND
+#if !IM_RND && !IM_LVL
         if (backlog) R_(true, false);
         else R_(false, false);
 #endif
@@ -2193,7 +2263,11 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
     // RANDOM: the same rows, from the RND translation unit (invmgmt_rnd.hip)
     if (pol && pol->kind == POL_RANDOM) return im_rnd_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
 #endif
-#if !IM_RND && !IM_EXT
+#if !IM_RND && !IM_LVL
+    // LEVELS: the same rows again, from the LVL translation unit (invmgmt_lvl.hip)
+    if (pol && pol->kind == POL_LEVELS) return im_lvl_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
+#endif
+#if !IM_RND && !IM_LVL && !IM_EXT
     // EXTERNAL: the caller's actions, the run kernel of invmgmt_ext.hip for any K
     if (pol && pol->kind == POL_EXTERNAL) return im_ext_launch(p, M1, backlog, t_u, *pol, io, ph, s);
 #endif
@@ -2263,13 +2337,13 @@ hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const
     if (philox) return im_ext_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, s);
     return im_ext_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, s);
 }
-#elif IM_RND
-// invmgmt_rnd.hip: this file compiled a third time, for the RANDOM variants of
-// the policy kernels of both demand streams: im_roll3o_kernel / im_roll3_kernel
-// where im_roll_applies (the rows of BaseStock / ConstantOrder),
-// im_run_kernel otherwise.
+#elif IM_RND || IM_LVL
+// invmgmt_rnd.hip / invmgmt_lvl.hip: this file compiled again, for the RANDOM /
+// LEVELS variants of the policy kernels of both demand streams: im_roll3o_kernel
+// / im_roll3_kernel where im_roll_applies (the rows of BaseStock /
+// ConstantOrder), im_run_kernel otherwise.
 template <class RG>
-static hipError_t im_rnd_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+static hipError_t im_var_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                                    const StepIO<int64_t, int64_t> &io, bool &sunk, hipStream_t s) {
     if (im_roll_applies(p, M1, t_u, &pol, io)) {
         sunk = true;
@@ -2294,10 +2368,15 @@ static hipError_t im_rnd_launch_rg(const ImParams &p, int M1, bool backlog, int 
 #undef KR_
     return hipGetLastError();
 }
+#if IM_LVL
+hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
+#else
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
-    if (philox) return im_rnd_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, sunk, s);
-    return im_rnd_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, sunk, s);
+#endif
+    if (philox) return im_var_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, sunk, s);
+    return im_var_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, sunk, s);
 }
 #elif defined(INVSIM_IM_FAST_TU)
 // invmgmt_ph.hip: this file compiled a second time for the fast-stream
@@ -2336,7 +2415,7 @@ INVSIM_PTRS_STATS_TU(im)
 
 }  // namespace invsim
 
-#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND && !IM_EXT
+#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND && !IM_EXT && !IM_LVL
 extern "C" int invsim_debug_timing(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbuf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }

@@ -398,17 +398,21 @@ struct StepIO {
 // argument; for InvMgmt the translation unit invmgmt_ext.hip, INVSIM_IM_EXT_TU),
 // so no existing instantiation gains a branch.
 enum { POL_NONE = 0, POL_CONSTANT = 1, POL_BASE_STOCK = 2, POL_ORDER_UP_TO = 3, POL_CLASSIC_NV = 4,
-       POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7 };
+       POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7, POL_LEVELS = 8 };
 constexpr int POL_MAX_A = 32;
 struct PolicyIO {
     int32_t kind;
     int32_t mdim;             // metrics per env (0: none)
     int32_t variant;          // CLASSIC_NV: 0 'k_vs_h', 1 'profit_margin'
     int32_t pad_;
-    double sf;                // safety factor (SS: S_buffer_factor)
+    union {                   // (one slot, as below)
+        double sf;            // safety factor (SS: S_buffer_factor)
+        const double *reorder;  // LEVELS: per-env reorder points [N][action_dim], or null
+    };
     union {                   // (one slot: the struct keeps the size every policy kernel's arguments had)
         double mu;            // BASE_STOCK: demand mean
         uint64_t *arng;       // RANDOM: the action generators [4][Npad] (act_rng_rows)
+        const double *levels; // LEVELS: per-env order-up-to levels [N][action_dim]
     };
     int64_t ci[POL_MAX_A];    // CONSTANT actions (RANDOM: the upper bounds), int64 action spaces
     float cf[POL_MAX_A];      // CONSTANT actions (RANDOM: the upper bounds), f32 action spaces
@@ -681,6 +685,9 @@ hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bo
 // the RANDOM (RND) instantiations of im_run_kernel, invmgmt_rnd.hip (both demand streams)
 // (the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
+// the LEVELS instantiations of the same kernels, invmgmt_lvl.hip (pol.levels / pol.reorder: [N][M1])
+hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
 // the EXTERNAL instantiations of im_run_kernel, invmgmt_ext.hip (both demand streams):
 // K >= 1 steps with the actions of io.act and the bookkeeping of pol (the rows are not sunk)

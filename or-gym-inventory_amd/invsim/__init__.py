@@ -29,6 +29,9 @@ _LAZY = {
     "RandomAgent": "policies",
     "TorchPolicyAgent": "policies",
     "MLPPolicyAgent": "policies",
+    "LevelsAgent": "policies",
+    "evaluate_levels": "policies",
+    "tune_levels": "policies",
     "convert_actions": "policies",
     "evaluate_agent": "policies",
     "rollout_policy": "policies",

@@ -51,6 +51,9 @@ class StepGraph:
     so that the demand lookahead is primed before the position is recorded).
     ``outputs`` is what ``fn`` returned during capture: static tensors the
     replays overwrite.  ``steps`` is the number of env steps one replay runs.
+    The graph keeps the tensors attached to the env at capture (a
+    ``LevelsAgent``'s, ``RandomAgent``'s generators) alive and reads them at
+    every replay, also after another agent has attached its own.
     """
 
     def __init__(self, env, fn, warmup=1, pool=None):
@@ -84,6 +87,10 @@ class StepGraph:
             raise
         self.outputs = out
         self.steps = int(steps.value)
+        # the launches recorded the addresses of the env's attached buffers (a
+        # LevelsAgent's levels / reorder points, RandomAgent's action generators):
+        # they live as long as the graph, whatever is attached to the env later
+        self._attached = (getattr(env, "_levels", None), getattr(env, "_arng", None))
 
     def replay(self):
         """Run the recorded loop once (on the current stream); returns ``outputs``."""

@@ -23,6 +23,13 @@ Agents (restated from the reference, same names and constructor arguments):
   match: the actions are numpy's ``Generator.uniform`` on a per-env PCG64
   stream of their own (``include/invsim.h``, "RandomAgent")
 
+* ``LevelsAgent(levels, reorder)`` BaseStock's rule with the order-up-to level
+  (and optionally the reorder point) of every env and stage read from a device
+  tensor, InvMgmt envs: one launch scores ``num_envs`` level vectors.
+  ``evaluate_levels`` scores ``[C, A]`` candidates on common seeds in one
+  launch and ``tune_levels`` searches them (``include/invsim.h``, "Per-env
+  base-stock levels")
+
 Policies computed outside the kernels (a trained ``torch.nn.Module`` actor, the
 scripts' ``SB3AgentWrapper``: benchmark_InvManagementBacklogEnv.py:332-342) go
 through ``TorchPolicyAgent(fn)``: the network runs in torch on the env's device
@@ -182,6 +189,76 @@ class RandomAgent(_Agent):
             env._attach_action_rng(buf)
         high = env._action_high()
         return _capi.PolicySpec(_capi.POLICY_KINDS["random"], 0, 0.0, 0.0, high.ctypes.data), high
+
+
+class LevelsAgent(_Agent):
+    """Order up to a level of the env's own, per stage: BaseStockAgent's rule
+    (order ``level - inventory position``, clipped to ``[0, c]``) with ``levels``
+    in place of ``(L + 1) * mu * safety_factor``, and with ``reorder`` only
+    while the position is strictly below the reorder point (an (s, S) policy).
+    ``levels`` / ``reorder``: array-likes or tensors ``[A]`` (every env alike) or
+    ``[N, A]`` (env n's own row), held as contiguous float64 tensors on the
+    env's device and attached to it for the launch
+    (``invsim_set_policy_levels``).  A tensor is used in place exactly when it is
+    float64, ``[N, A]``, contiguous and on the env's GPU: the kernels read it when
+    they run, so in-place updates (also between replays of a captured graph) are
+    seen by the next launch.  Anything else (another dtype, shape ``[A]``, a
+    non-contiguous view, the host, another GPU) is copied once, when the agent
+    first meets the env, and later changes to the original are not seen;
+    ``agent.tensors(env)`` returns the pair the kernels read, whichever it is.
+    Under ``env.capture`` let the agent meet the env (``device_spec``) before the
+    capture: attaching is refused inside one.  A captured graph holds the
+    addresses of the tensors attached when it was recorded; the ``StepGraph``
+    keeps those tensors alive, and replaying it reads them whichever agent is
+    attached by then."""
+
+    def __init__(self, levels, reorder=None, name="Levels"):
+        self.levels = levels
+        self.reorder = reorder
+        self.name = name
+        self._bufs = weakref.WeakKeyDictionary()       # env -> (levels, reorder) on its device
+
+    @classmethod
+    def from_safety_factor(cls, env, sf, **kw):
+        """The levels BaseStockAgent(sf) orders up to on ``env``, ``(lead_time +
+        1) * mu * sf`` evaluated in numpy in that order with the agent's own
+        ``mu`` default; ``sf`` a scalar, ``[N]`` or ``[N, A]``.  With a scalar the
+        rollouts equal BaseStockAgent's bit for bit."""
+        mu = env.dist_param.get("mu", 10)
+        sf = np.asarray(sf, np.float64)
+        if sf.ndim == 1:
+            sf = sf[:, None]
+        return cls((env.lead_time + 1) * mu * sf, **kw)
+
+    def _on_device(self, env, a, what):
+        N, A = env.num_envs, env.action_dim
+        if (type(a) is torch.Tensor and a.dtype == torch.float64 and a.is_cuda
+                and a.get_device() == env.device_index     # the resolved index: "cuda" without one is the current device
+                and a.is_contiguous() and tuple(a.shape) == (N, A)):
+            return a                                   # in place
+        t = torch.as_tensor(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, np.float64))
+        if tuple(t.shape) == (A,):
+            t = t.expand(N, A)
+        if tuple(t.shape) != (N, A):
+            raise ValueError(f"{what} must have shape {(A,)} or {(N, A)}, got {tuple(t.shape)}")
+        return t.contiguous().to(env.device)
+
+    def tensors(self, env):
+        """(levels, reorder or None): the float64 ``[N, A]`` device tensors the
+        kernels read for this agent on ``env`` (made at the first call)."""
+        if env.family != _capi.INVSIM_INVMGMT:
+            raise TypeError("LevelsAgent needs an InvManagement env")
+        bufs = self._bufs.get(env)
+        if bufs is None:
+            bufs = (self._on_device(env, self.levels, "levels"),
+                    None if self.reorder is None else self._on_device(env, self.reorder, "reorder"))
+            self._bufs[env] = bufs
+        return bufs
+
+    def device_spec(self, env):
+        bufs = self.tensors(env)
+        env._attach_policy_levels(*bufs)               # (kept alive by the env while attached)
+        return _capi.PolicySpec(_capi.POLICY_KINDS["levels"], 0, 0.0, 0.0, None), bufs
 
 
 def convert_actions(raw, low, high, dtype):
@@ -601,3 +678,112 @@ def summary_table(results):
     return summary[["AvgReward", "MedianReward", "StdReward", "MinReward", "MaxReward", "AvgServiceLevel",
                     "AvgStockoutQty", "AvgEndInv", "AvgTimePerEp", "TrainingTime(s)", "SuccessfulEpisodes",
                     "EpisodesAttempted", "SuccessRate(%)"]]
+
+
+def _levels_env(env_cls, env_config, n_cand, n_episodes, seed_offset, device):
+    """One env of n_cand * n_episodes instances; instance c * n_episodes + r
+    will run candidate c on seed seed_offset + r (the returned seed list)."""
+    env = env_cls(num_envs=n_cand * n_episodes, device=device, autoreset_mode="disabled", **(env_config or {}))
+    if env.family != _capi.INVSIM_INVMGMT:
+        env.close()
+        raise TypeError("level policies need an InvManagement env class")
+    return env, [seed_offset + r for _ in range(n_cand) for r in range(n_episodes)]
+
+
+def _levels_columns(family, met, n_cand, n_episodes):
+    """summarize()'s columns as [C, R] and, under "candidates", the per-candidate
+    means summary_table() reports, each [C] (StdReward: the sample standard
+    deviation)."""
+    cols = {k: np.ascontiguousarray(v.reshape(n_cand, n_episodes)) for k, v in summarize(family, met).items()}
+    # one contiguous row at a time: the very sum np.mean takes over an evaluate_agent column
+    mean = lambda a: np.array([np.mean(row) for row in a])  # noqa: E731
+    cols["candidates"] = {
+        "AvgReward": mean(cols["TotalReward"]),
+        "StdReward": np.array([np.std(row, ddof=1) if n_episodes > 1 else np.nan for row in cols["TotalReward"]]),
+        "AvgServiceLevel": mean(cols["AvgServiceLevel"]), "AvgEndingInv": mean(cols["AvgEndingInv"])}
+    return cols
+
+
+def evaluate_levels(levels, env_cls, env_config=None, n_episodes=100, seed_offset=0, reorder=None, device=None):
+    """Score ``levels`` [C, A] (and ``reorder`` [C, A]) candidates under common
+    random numbers: one env of ``C * n_episodes`` instances, instance ``c *
+    n_episodes + r`` running candidate c on seed ``seed_offset + r``, one full
+    episode in one launch, metrics only.  Returns a dict: ``TotalReward`` and
+    the other ``summarize`` columns as ``[C, n_episodes]`` (row c equals
+    ``evaluate_agent(LevelsAgent(levels[c]), ...)`` on the same seeds, bit for
+    bit), and under ``"candidates"`` a dict of the per-candidate ``AvgReward``,
+    ``StdReward``, ``AvgServiceLevel`` and ``AvgEndingInv``, each ``[C]`` (the
+    means of those rows; the per-episode columns keep the two shared names)."""
+    rows = lambda a: np.repeat(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a,  # noqa: E731
+                                          np.float64), n_episodes, axis=0)
+    lv = rows(levels)
+    if lv.ndim != 2:
+        raise ValueError(f"levels must be [C, A], got {np.shape(levels)}")
+    n_cand = lv.shape[0] // n_episodes
+    env, seeds = _levels_env(env_cls, env_config, n_cand, n_episodes, seed_offset, device)
+    try:
+        env.reset(seed=seeds)
+        met = torch.zeros((env.num_envs, metrics_dim(env)), dtype=torch.float64, device=env.device)
+        agent = LevelsAgent(lv, None if reorder is None else rows(reorder))
+        rollout_policy(env, agent, env._horizon(), obs=False, rewards=False, metrics=met)
+        return _levels_columns(env.family, met.cpu().numpy(), n_cand, n_episodes)
+    finally:
+        env.close()
+
+
+def tune_levels(env_cls, env_config=None, n_episodes=64, population=256, iterations=10, seed=0, seed_offset=0,
+                init=None, elite_frac=0.1, device=None, max_level=None):
+    """Cross-entropy search for the level vector with the best mean episode
+    reward over seeds ``seed_offset .. seed_offset + n_episodes - 1``.
+
+    One env of ``population * n_episodes`` instances and one levels tensor are
+    made once; an iteration is ``reset(seed=<the same list>)``, an in-place
+    rewrite of the levels tensor and one launch of one episode.  Candidates are
+    drawn from a diagonal normal (a seeded ``torch.Generator``), clipped to
+    ``[0, max_level]`` and refitted to the best ``elite_frac`` of them.
+    ``max_level`` defaults per stage to ``max(3 * (L + 1) * mu, c)``: a few
+    multiples of BaseStock's level, and never so low that an order of the full
+    capacity ``c`` is out of reach.  Candidate 0 of every generation is the
+    incumbent best (``init``, default the ``safety_factor = 1`` levels, in the
+    first): the same seeds and levels give the same bits, so its score is
+    reproduced exactly and the best score never decreases.
+
+    Returns a dict: ``levels`` [A] the best vector, ``TotalReward``
+    [n_episodes] its per-episode rewards, ``history`` [iterations] the best
+    ``AvgReward`` after each iteration."""
+    if population < 2 or iterations < 1:
+        raise ValueError("tune_levels needs population >= 2 and iterations >= 1")
+    env, seeds = _levels_env(env_cls, env_config, population, n_episodes, seed_offset, device)
+    try:
+        A = env.action_dim
+        base = np.asarray((env.lead_time + 1) * env.dist_param.get("mu", 10), np.float64)
+        hi = np.maximum(3.0 * base, env.supply_capacity.astype(np.float64)) if max_level is None else \
+            np.broadcast_to(np.asarray(max_level, np.float64), (A,))
+        hi = torch.from_numpy(np.ascontiguousarray(hi))
+        best = torch.as_tensor(np.asarray(base if init is None else init, np.float64)).reshape(A).clone()
+        mean, std = best.clone(), hi / 4
+        gen = torch.Generator().manual_seed(int(seed))
+        n_elite = max(2, int(round(elite_frac * population)))
+        lv = torch.empty((env.num_envs, A), dtype=torch.float64, device=env.device)
+        agent = LevelsAgent(lv)
+        met = torch.zeros((env.num_envs, metrics_dim(env)), dtype=torch.float64, device=env.device)
+        history, best_rew = [], None
+        for _ in range(iterations):
+            cand = mean + std * torch.randn((population, A), dtype=torch.float64, generator=gen)
+            cand = torch.minimum(torch.clamp(cand, min=0.0), hi)
+            cand[0] = best
+            env.reset(seed=seeds)
+            lv.copy_(cand.repeat_interleave(n_episodes, dim=0))
+            met.zero_()
+            rollout_policy(env, agent, env._horizon(), obs=False, rewards=False, metrics=met)
+            cols = _levels_columns(env.family, met.cpu().numpy(), population, n_episodes)
+            avg = cols["candidates"]["AvgReward"]
+            order = np.argsort(-avg, kind="stable")                     # (ties: the incumbent first)
+            top = int(order[0])
+            best, best_rew = cand[top].clone(), cols["TotalReward"][top].copy()
+            history.append(float(avg[top]))
+            elite = cand[torch.from_numpy(order[:n_elite].copy())]
+            mean, std = elite.mean(dim=0), elite.std(dim=0).clamp_min(1e-3)
+        return {"levels": best.numpy(), "TotalReward": best_rew, "history": np.asarray(history)}
+    finally:
+        env.close()

@@ -112,6 +112,7 @@ class InvSimVectorEnv:
             _capi.check(self._lib.invsim_set_info_record(self._h, self._rec.data_ptr()), self._h, "set_info_record")
         self._out = None
         self._arng = None     # RandomAgent's action generators (seed_actions)
+        self._levels = None   # LevelsAgent's attached (levels, reorder) tensors (_attach_policy_levels)
         self._mlps = []       # invsim_mlp objects of MLPPolicyAgents that met this env (destroyed in close)
 
     def _record_info(self, info):
@@ -354,6 +355,16 @@ class InvSimVectorEnv:
         _capi.check(self._lib.invsim_set_action_rng(self._h, buf.data_ptr() if buf is not None else None),
                     self._h, "set_action_rng")
         self._arng = buf
+
+    def _attach_policy_levels(self, levels, reorder=None):
+        """Attach the LEVELS policy's device tensors (float64 [N, A]); they stay
+        alive here while attached.  Nothing to do when they already are."""
+        cur = self._levels
+        if cur is not None and cur[0] is levels and cur[1] is reorder:
+            return
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _capi.check(self._lib.invsim_set_policy_levels(self._h, p(levels), p(reorder)), self._h, "set_policy_levels")
+        self._levels = (levels, reorder) if levels is not None else None
 
     def seed_actions(self, seed):
         """Allocate, seed and attach the per-env action generators: env i draws
