@@ -520,7 +520,56 @@ int invsim_debug_ptrs_stats(uint64_t *out, int32_t clear);
  * ("philox_step"; the first fast-stream call after set_state reads it back,
  * synchronously).  Switching streams synchronises the device (work queued on
  * any stream finishes first); the PCG64 states are untouched by fast-stream
- * steps. */
+ * steps.
+ *
+ * The fast stream, exactly (the CPU oracle restates this text, oracle/oracle.c,
+ * and tests/test_gpu_philox_oracle.py holds every kernel to it bit for bit):
+ *   block      x = Philox4x32-10(counter (j, r, s_lo, s_hi), key): j the block
+ *              index of the draw, r its draw stream, s the 64-bit launch step
+ *              (low word counter word 2, high word counter word 3).
+ *   key        the env's `rng` row 2 (PCG64 increment, high word) as seeded:
+ *              low 32 bits key word 0, high 32 bits key word 1.  A reseed of an
+ *              env re-keys it; nothing else does.
+ *   outputs    a block gives two 64-bit outputs, (x.y:x.x) then (x.w:x.z); a
+ *              uniform double is (output >> 11) * 2**-53.  A draw starts at
+ *              block j = 0 of its (s, r) with no output held over, and a
+ *              sampler that needs more (a PTRS rejection, a longer product)
+ *              continues with the held second output, then j = 1, 2, ...  A
+ *              second output left unused by a draw is dropped, never given to
+ *              another draw.  The 32-bit half that numpy's integers() buffers
+ *              is empty at the start of every launch step (within a Net step
+ *              it passes from one integers market to the next, as numpy's
+ *              does), and the `u32buf` state field is neither read nor written.
+ *   streams    r = 0: the demand of InvMgmt and Newsvendor.  Net: market r of
+ *              the step draws from stream r, r its index in retail-link order,
+ *              counting the markets that draw nothing (user_D replays and
+ *              markets without a demand source) too.  r = 0xffffffff (RESET):
+ *              the five uniforms of a Newsvendor reset, in the reference's
+ *              order (price, cost, h, k, mu).  dist 5 (user_D) draws nothing.
+ *   counter    one per handle, 0 at create and after an unmasked seed
+ *              (invsim_seed_range / invsim_seed_words with mask == NULL); a
+ *              masked seed keeps it.  Launch step k of a step / rollout /
+ *              policy-rollout call of K steps uses s + k for every env, whatever
+ *              the env's own period; the call then adds K.  Switching streams
+ *              keeps it; steps on the numpy stream do not advance it.
+ *   resets     A NEXT_STEP reset step is a launch step like any other: it
+ *              consumes its counter value; InvMgmt and Net draw nothing in it,
+ *              Newsvendor draws the reset's uniforms from stream RESET at that
+ *              value.  A SAME_STEP autoreset happens inside the done step and
+ *              has no value of its own: Newsvendor draws the new episode's
+ *              uniforms from stream RESET at the done step's value (its demand
+ *              came from stream 0 of the same value).  invsim_reset, masked or
+ *              not: InvMgmt and Net leave the counter alone; on Newsvendor the
+ *              reset envs draw from stream RESET at the current value s and the
+ *              handle's counter becomes s + 1 (for every env, also under a mask).
+ *   lookahead  a kernel may draw launch step s + 1 while it applies step s;
+ *              the draw is the one of (key, s + 1, r) and is discarded when
+ *              the counter or a key moves (seed, set_state, reset, a switch).
+ *   capture    no two draws of one env ever share a block: (s, r) differs
+ *              between any two draws, because every call that draws consumes
+ *              the values it uses.  A captured launch would break this (s is a
+ *              launch parameter and would repeat on replay), so capture on the
+ *              fast stream is refused (INVSIM_EINVAL). */
 #define INVSIM_DEMAND_NUMPY 0
 #define INVSIM_DEMAND_PHILOX 1
 int invsim_set_demand_stream(invsim_handle *h, int32_t mode);

@@ -95,6 +95,117 @@ double orc_next_double(uint64_t rng[4]) {
     return (double)(orc_next64(rng) >> 11) * (1.0 / 9007199254740992.0);
 }
 
+/* ======================================================================
+ * The fast demand stream (include/invsim.h INVSIM_DEMAND_PHILOX;
+ * csrc/device_common.hpp PhiloxGen), restated from the Philox4x32-10
+ * definition (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3",
+ * SC'11; Random123 philox.h): ten rounds of
+ *     hi0:lo0 = M0 * c0,  hi1:lo1 = M1 * c2
+ *     c' = (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0)
+ * with the key bumped by (W0, W1) between rounds.
+ * ==================================================================== */
+#define PHILOX_M0 0xD2511F53u
+#define PHILOX_M1 0xCD9E8D57u
+#define PHILOX_W0 0x9E3779B9u
+#define PHILOX_W1 0xBB67AE85u
+
+void orc_philox_block(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
+    uint32_t k0 = key[0], k1 = key[1];
+    for (int round = 0; round < 10; round++) {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0;
+        const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += PHILOX_W0;
+        k1 += PHILOX_W1;
+    }
+    out[0] = c0;
+    out[1] = c1;
+    out[2] = c2;
+    out[3] = c3;
+}
+
+/* key = the env's PCG64 increment high word (rng row 2): low half key.x */
+void orc_philox_init(orc_philox *g, uint64_t key64) {
+    memset(g, 0, sizeof(*g));
+    g->key[0] = (uint32_t)key64;
+    g->key[1] = (uint32_t)(key64 >> 32);
+}
+
+/* the launch step; the block index and the held half are sub()'s to restart */
+void orc_philox_set_step(orc_philox *g, uint64_t s) {
+    g->s0 = (uint32_t)s;
+    g->s1 = (uint32_t)(s >> 32);
+}
+
+void orc_philox_sub(orc_philox *g, uint32_t r) {
+    g->r = r;
+    g->j = 0;
+    g->have = 0;
+}
+
+/* counter (j, r, s_lo, s_hi); a block is two 64-bit outputs, (x.y:x.x) then (x.w:x.z) */
+uint64_t orc_philox_next64(orc_philox *g) {
+    if (g->have) {
+        g->have = 0;
+        return g->hold;
+    }
+    const uint32_t ctr[4] = {g->j, g->r, g->s0, g->s1};
+    uint32_t x[4];
+    orc_philox_block(ctr, g->key, x);
+    g->j++;
+    g->hold = ((uint64_t)x[3] << 32) | x[2];
+    g->have = 1;
+    return ((uint64_t)x[1] << 32) | x[0];
+}
+
+double orc_philox_next_double(orc_philox *g) {
+    return (double)(orc_philox_next64(g) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+/* What the samplers below draw from: an env's PCG64 state (numpy's stream) or
+ * a positioned Philox generator (the fast stream).  One sampler text, either
+ * source. */
+typedef struct {
+    uint64_t *pcg;  /* rng[4] of the numpy stream, or NULL */
+    orc_philox ph;  /* the fast stream otherwise */
+} orc_gen;
+
+static orc_gen gen_pcg(uint64_t rng[4]) {
+    orc_gen g;
+    g.pcg = rng;
+    return g;
+}
+
+static uint64_t gen_next64(orc_gen *g) { return g->pcg ? orc_next64(g->pcg) : orc_philox_next64(&g->ph); }
+
+static double gen_double(orc_gen *g) {
+    return (double)(gen_next64(g) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+/* an env's generator for launch step `step`, positioned at draw stream 0 */
+static orc_gen gen_env(int stream, uint64_t rng[4], uint64_t step) {
+    orc_gen g;
+    if (stream == ORC_STREAM_NUMPY) {
+        g.pcg = rng;
+        return g;
+    }
+    g.pcg = NULL;
+    orc_philox_init(&g.ph, rng[2]);
+    orc_philox_set_step(&g.ph, step);
+    orc_philox_sub(&g.ph, 0);
+    return g;
+}
+
+static void gen_sub(orc_gen *g, uint32_t r) {
+    if (!g->pcg) orc_philox_sub(&g->ph, r);
+}
+
 /* numpy distributions.c random_loggam */
 double orc_loggam(double x) {
     static const double a[10] = {8.333333333333333e-02, -2.777777777777778e-03,
@@ -126,8 +237,18 @@ double orc_loggam(double x) {
     return gl;
 }
 
+/* Branch counters (orc_dist_fill_counted, oracle.h ORC_C_*): every sampler
+ * below takes `cnt`, the caller's own array or NULL for no counting, down as
+ * an argument; nothing here is shared between callers, so the env loops
+ * (which pass NULL through the orc_* entry points) stay free of shared state. */
+#define CNT(i)              \
+    do {                    \
+        if (cnt) cnt[i]++;  \
+    } while (0)
+
 /* numpy distributions.c random_poisson_ptrs (lam >= 10) */
-static int64_t poisson_ptrs(uint64_t rng[4], double lam) {
+static int64_t poisson_ptrs(orc_gen *g, double lam, int64_t *cnt) {
+    CNT(ORC_C_POIS_PTRS);
     double slam = sqrt(lam);
     double loglam = log(lam);
     double b = 0.931 + 2.53 * slam;
@@ -135,37 +256,50 @@ static int64_t poisson_ptrs(uint64_t rng[4], double lam) {
     double invalpha = 1.1239 + 1.1328 / (b - 3.4);
     double vr = 0.9277 - 3.6224 / (b - 2);
     for (;;) {
-        double U = orc_next_double(rng) - 0.5;
-        double V = orc_next_double(rng);
+        double U = gen_double(g) - 0.5;
+        double V = gen_double(g);
         double us = 0.5 - fabs(U);
         int64_t k = (int64_t)floor((2 * a / us + b) * U + lam + 0.43);
         if ((us >= 0.07) && (V <= vr)) return k;
-        if ((k < 0) || ((us < 0.013) && (V > us))) continue;
+        if ((k < 0) || ((us < 0.013) && (V > us))) {
+            CNT(ORC_C_POIS_PTRS_REJECT);
+            continue;
+        }
         if ((log(V) + log(invalpha) - log(a / (us * us) + b)) <=
             (-lam + k * loglam - orc_loggam(k + 1)))
             return k;
+        CNT(ORC_C_POIS_PTRS_REJECT);
     }
 }
 
 /* numpy distributions.c random_poisson_mult (0 < lam < 10) */
-static int64_t poisson_mult(uint64_t rng[4], double lam) {
+static int64_t poisson_mult(orc_gen *g, double lam, int64_t *cnt) {
+    CNT(ORC_C_POIS_MULT);
     double enlam = exp(-lam);
     int64_t X = 0;
     double prod = 1.0;
     for (;;) {
-        double U = orc_next_double(rng);
+        double U = gen_double(g);
         prod *= U;
-        if (prod > enlam)
+        if (prod > enlam) {
             X += 1;
-        else
+        } else {
+            if (!(X & 1)) CNT(ORC_C_POIS_MULT_ODD); /* X + 1 uniforms: an odd count */
             return X;
+        }
     }
 }
 
-int64_t orc_poisson(uint64_t rng[4], double lam) {
-    if (lam >= 10) return poisson_ptrs(rng, lam);
+/* random_poisson */
+static int64_t poisson_c(orc_gen *g, double lam, int64_t *cnt) {
+    if (lam >= 10) return poisson_ptrs(g, lam, cnt);
     if (lam == 0) return 0;
-    return poisson_mult(rng, lam);
+    return poisson_mult(g, lam, cnt);
+}
+
+int64_t orc_poisson(uint64_t rng[4], double lam) {
+    orc_gen g = gen_pcg(rng);
+    return poisson_c(&g, lam, NULL);
 }
 
 void orc_poisson_fill(uint64_t rng[4], double lam, int64_t *out, int64_t n) {
@@ -176,31 +310,27 @@ void orc_poisson_fill(uint64_t rng[4], double lam, int64_t *out, int64_t n) {
  * random/src/distributions/distributions.c + pcg64.h), the demand samplers of
  * inventory_management.py:173-182 (dist 2, 3, 4). */
 
-/* Branch counters (orc_dist_fill_counted, oracle.h ORC_C_*): every sampler
- * below takes `cnt`, the caller's own array or NULL for no counting, down as
- * an argument; nothing here is shared between callers, so the env loops
- * (which pass NULL through the orc_* entry points) stay free of shared state. */
-#define CNT(i)              \
-    do {                    \
-        if (cnt) cnt[i]++;  \
-    } while (0)
-
 /* pcg64_next32: the low half of a 64-bit output first, the high half buffered
  * in the bit generator (has_uint32 / uinteger) for the next 32-bit draw */
-uint32_t orc_next32(uint64_t rng[4], uint32_t *buf /* [2]: has, value */) {
+static uint32_t gen_next32(orc_gen *g, uint32_t *buf /* [2]: has, value */) {
     if (buf[0]) {
         buf[0] = 0;
         return buf[1];
     }
-    uint64_t x = orc_next64(rng);
+    uint64_t x = gen_next64(g);
     buf[0] = 1;
     buf[1] = (uint32_t)(x >> 32);
     return (uint32_t)x;
 }
 
+uint32_t orc_next32(uint64_t rng[4], uint32_t *buf) {
+    orc_gen g = gen_pcg(rng);
+    return gen_next32(&g, buf);
+}
+
 /* random_bounded_uint64_fill(cnt = 1, use_masked = false): off + [0, rng] via
  * Lemire's method (32-bit buffered draws when rng fits in 32 bits) */
-static uint64_t bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64_t r, int64_t *cnt) {
+static uint64_t bounded_uint64(orc_gen *g, uint32_t *buf, uint64_t off, uint64_t r, int64_t *cnt) {
     if (r == 0) {
         CNT(ORC_C_INT_CONST);
         return off;
@@ -208,32 +338,32 @@ static uint64_t bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uin
     if (r <= 0xFFFFFFFFULL) {
         if (r == 0xFFFFFFFFULL) {
             CNT(ORC_C_INT_FULL32);
-            return off + orc_next32(rng, buf);
+            return off + gen_next32(g, buf);
         }
         CNT(ORC_C_INT32_DRAW);
         const uint32_t rng_excl = (uint32_t)r + 1;
-        uint64_t m = (uint64_t)orc_next32(rng, buf) * rng_excl;
+        uint64_t m = (uint64_t)gen_next32(g, buf) * rng_excl;
         uint32_t leftover = (uint32_t)m;
         if (leftover < rng_excl) {
             const uint32_t threshold = (uint32_t)((UINT32_MAX - (uint32_t)r) % rng_excl);
             while (leftover < threshold) {
                 CNT(ORC_C_INT32_REJECT);
-                m = (uint64_t)orc_next32(rng, buf) * rng_excl;
+                m = (uint64_t)gen_next32(g, buf) * rng_excl;
                 leftover = (uint32_t)m;
             }
         }
         return off + (m >> 32);
     }
-    if (r == 0xFFFFFFFFFFFFFFFFULL) return off + orc_next64(rng);
+    if (r == 0xFFFFFFFFFFFFFFFFULL) return off + gen_next64(g);
     CNT(ORC_C_INT64_DRAW);
     const uint64_t rng_excl = r + 1;
-    u128 m = (u128)orc_next64(rng) * rng_excl;
+    u128 m = (u128)gen_next64(g) * rng_excl;
     uint64_t leftover = (uint64_t)m;
     if (leftover < rng_excl) {
         const uint64_t threshold = (UINT64_MAX - r) % rng_excl;
         while (leftover < threshold) {
             CNT(ORC_C_INT64_REJECT);
-            m = (u128)orc_next64(rng) * rng_excl;
+            m = (u128)gen_next64(g) * rng_excl;
             leftover = (uint64_t)m;
         }
     }
@@ -241,28 +371,30 @@ static uint64_t bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uin
 }
 
 uint64_t orc_bounded_uint64(uint64_t rng[4], uint32_t *buf, uint64_t off, uint64_t r) {
-    return bounded_uint64(rng, buf, off, r, NULL);
+    orc_gen g = gen_pcg(rng);
+    return bounded_uint64(&g, buf, off, r, NULL);
 }
 
 /* Generator.integers(low, high) (high exclusive, int64) */
-static int64_t integers_c(uint64_t rng[4], uint32_t *buf, int64_t low, int64_t high, int64_t *cnt) {
+static int64_t integers_c(orc_gen *g, uint32_t *buf, int64_t low, int64_t high, int64_t *cnt) {
     const uint64_t r = (uint64_t)high - (uint64_t)low - 1;
-    return (int64_t)bounded_uint64(rng, buf, (uint64_t)low, r, cnt);
+    return (int64_t)bounded_uint64(g, buf, (uint64_t)low, r, cnt);
 }
 
 int64_t orc_integers(uint64_t rng[4], uint32_t *buf, int64_t low, int64_t high) {
-    return integers_c(rng, buf, low, high, NULL);
+    orc_gen g = gen_pcg(rng);
+    return integers_c(&g, buf, low, high, NULL);
 }
 
 /* random_binomial_inversion (n * p <= 30) */
-static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
+static int64_t binomial_inversion(orc_gen *g, int64_t n, double p, int64_t *cnt) {
     const double q = 1.0 - p;
     const double qn = exp(n * log(q));
     const double np = n * p;
     const int64_t bound = (int64_t)fmin((double)n, np + 10.0 * sqrt(np * q + 1));
     int64_t X = 0;
     double px = qn;
-    double U = orc_next_double(rng);
+    double U = gen_double(g);
     CNT(ORC_C_BINOM_INVERSION);
     while (U > px) {
         X++;
@@ -270,7 +402,7 @@ static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p, int64_t 
             CNT(ORC_C_INV_RESTART);
             X = 0;
             px = qn;
-            U = orc_next_double(rng);
+            U = gen_double(g);
         } else {
             U -= px;
             px = ((n - X + 1) * p * px) / (X * q);
@@ -280,7 +412,7 @@ static int64_t binomial_inversion(uint64_t rng[4], int64_t n, double p, int64_t 
 }
 
 /* random_binomial_btpe (n * p > 30, p <= 0.5) */
-static int64_t binomial_btpe(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
+static int64_t binomial_btpe(orc_gen *g, int64_t n, double p, int64_t *cnt) {
     const double r = fmin(p, 1.0 - p);
     const double q = 1.0 - r;
     const double fm = n * r + r;
@@ -301,8 +433,8 @@ static int64_t binomial_btpe(uint64_t rng[4], int64_t n, double p, int64_t *cnt)
     int64_t y, k, i;
 step10:
     nrq = n * r * q;
-    u = orc_next_double(rng) * p4;
-    v = orc_next_double(rng);
+    u = gen_double(g) * p4;
+    v = gen_double(g);
     if (u > p1) goto step20;
     CNT(ORC_C_BTPE_TRIANGLE);
     y = (int64_t)floor(xm - p1 * v + u);
@@ -380,22 +512,25 @@ step60:
 }
 
 /* random_binomial */
-static int64_t binomial_c(uint64_t rng[4], int64_t n, double p, int64_t *cnt) {
+static int64_t binomial_c(orc_gen *g, int64_t n, double p, int64_t *cnt) {
     if ((n == 0) || (p == 0.0f)) {
         CNT(ORC_C_BINOM_ZERO);
         return 0;
     }
     if (p <= 0.5) {
-        if (p * n <= 30.0) return binomial_inversion(rng, n, p, cnt);
-        return binomial_btpe(rng, n, p, cnt);
+        if (p * n <= 30.0) return binomial_inversion(g, n, p, cnt);
+        return binomial_btpe(g, n, p, cnt);
     }
     CNT(ORC_C_BINOM_FLIP);
     const double q = 1.0 - p;
-    if (q * n <= 30.0) return n - binomial_inversion(rng, n, q, cnt);
-    return n - binomial_btpe(rng, n, q, cnt);
+    if (q * n <= 30.0) return n - binomial_inversion(g, n, q, cnt);
+    return n - binomial_btpe(g, n, q, cnt);
 }
 
-int64_t orc_binomial(uint64_t rng[4], int64_t n, double p) { return binomial_c(rng, n, p, NULL); }
+int64_t orc_binomial(uint64_t rng[4], int64_t n, double p) {
+    orc_gen g = gen_pcg(rng);
+    return binomial_c(&g, n, p, NULL);
+}
 
 #include "numpy_ziggurat.h"
 #ifdef _OPENMP
@@ -416,9 +551,9 @@ int orc_max_threads(void) {
 }
 
 /* random_standard_exponential (256-level ziggurat, tables from numpy) */
-static double standard_exponential_c(uint64_t rng[4], int64_t *cnt) {
+static double standard_exponential_c(orc_gen *g, int64_t *cnt) {
     for (;;) {
-        uint64_t ri = orc_next64(rng);
+        uint64_t ri = gen_next64(g);
         ri >>= 3;
         const uint8_t idx = (uint8_t)(ri & 0xFF);
         ri >>= 8;
@@ -427,9 +562,9 @@ static double standard_exponential_c(uint64_t rng[4], int64_t *cnt) {
         CNT(ORC_C_ZIG_SLOW);
         if (idx == 0) {
             CNT(ORC_C_ZIG_TAIL);
-            return NPZ_EXP_R - log1p(-orc_next_double(rng));
+            return NPZ_EXP_R - log1p(-gen_double(g));
         }
-        if ((npz_fe[idx - 1] - npz_fe[idx]) * orc_next_double(rng) + npz_fe[idx] < exp(-x)) {
+        if ((npz_fe[idx - 1] - npz_fe[idx]) * gen_double(g) + npz_fe[idx] < exp(-x)) {
             CNT(ORC_C_ZIG_WEDGE_ACCEPT);
             return x;
         }
@@ -437,15 +572,18 @@ static double standard_exponential_c(uint64_t rng[4], int64_t *cnt) {
     }
 }
 
-double orc_standard_exponential(uint64_t rng[4]) { return standard_exponential_c(rng, NULL); }
+double orc_standard_exponential(uint64_t rng[4]) {
+    orc_gen g = gen_pcg(rng);
+    return standard_exponential_c(&g, NULL);
+}
 
 /* random_geometric: search for p >= 1/3, else inversion of the exponential */
-static int64_t geometric_c(uint64_t rng[4], double p, int64_t *cnt) {
+static int64_t geometric_c(orc_gen *g, double p, int64_t *cnt) {
     if (p >= 0.333333333333333333333333) {
         int64_t X = 1;
         double sum = p, prod = p;
         const double q = 1.0 - p;
-        const double U = orc_next_double(rng);
+        const double U = gen_double(g);
         while (U > sum) {
             CNT(ORC_C_GEOM_SEARCH);
             prod *= q;
@@ -455,7 +593,7 @@ static int64_t geometric_c(uint64_t rng[4], double p, int64_t *cnt) {
         return X;
     }
     CNT(ORC_C_GEOM_INVERSION);
-    const double z = ceil(-standard_exponential_c(rng, cnt) / log1p(-p));
+    const double z = ceil(-standard_exponential_c(g, cnt) / log1p(-p));
     if (z >= 9.223372036854776e+18) {
         CNT(ORC_C_GEOM_CLAMP);
         return INT64_MAX;
@@ -463,17 +601,42 @@ static int64_t geometric_c(uint64_t rng[4], double p, int64_t *cnt) {
     return (int64_t)z;
 }
 
-int64_t orc_geometric(uint64_t rng[4], double p) { return geometric_c(rng, p, NULL); }
+int64_t orc_geometric(uint64_t rng[4], double p) {
+    orc_gen g = gen_pcg(rng);
+    return geometric_c(&g, p, NULL);
+}
+
+/* one demand draw: dist 1 poisson(p), 2 binomial(n_or_low, p), 3 integers
+ * [n_or_low, high), 4 geometric(p) */
+static int64_t dist_draw(orc_gen *g, uint32_t *buf, int dist, int64_t n_or_low, int64_t high, double p, int64_t *cnt) {
+    if (dist == 1) return poisson_c(g, p, cnt);
+    if (dist == 2) return binomial_c(g, n_or_low, p, cnt);
+    if (dist == 3) return integers_c(g, buf, n_or_low, high, cnt);
+    if (dist == 4) return geometric_c(g, p, cnt);
+    return 0;
+}
 
 /* counts: NULL, or the caller's own int64[ORC_NCOUNT] that the draws add to */
 void orc_dist_fill_counted(uint64_t rng[4], uint32_t *buf, int dist, int64_t n_or_low, int64_t high, double p,
                            int64_t *out, int64_t count, int64_t *counts) {
-    int64_t *const cnt = counts;
+    orc_gen g = gen_pcg(rng);
+    for (int64_t i = 0; i < count; i++) out[i] = dist_draw(&g, buf, dist, n_or_low, high, p, counts);
+}
+
+/* The fast stream's draws of one env: launch steps step0 .. step0 + count - 1
+ * of draw stream r under `key64`, each from a fresh block sequence and with no
+ * 32-bit half carried in (the contract of include/invsim.h), through the same
+ * samplers; counts as above. */
+void orc_philox_dist_fill_counted(uint64_t key64, uint64_t step0, uint32_t r, int dist, int64_t n_or_low,
+                                  int64_t high, double p, int64_t *out, int64_t count, int64_t *counts) {
+    orc_gen g;
+    g.pcg = NULL;
+    orc_philox_init(&g.ph, key64);
     for (int64_t i = 0; i < count; i++) {
-        if (dist == 2) out[i] = binomial_c(rng, n_or_low, p, cnt);
-        else if (dist == 3) out[i] = integers_c(rng, buf, n_or_low, high, cnt);
-        else if (dist == 4) out[i] = geometric_c(rng, p, cnt);
-        else out[i] = 0;
+        uint32_t buf[2] = {0, 0};
+        orc_philox_set_step(&g.ph, step0 + (uint64_t)i);
+        orc_philox_sub(&g.ph, r);
+        out[i] = dist_draw(&g, buf, dist, n_or_low, high, p, counts);
     }
 }
 
@@ -585,6 +748,8 @@ typedef struct {
     double *par;    /* [n][5] price, cost, h, k, mu (Python floats) */
     float *state;   /* [n][L+5] self.state */
     int32_t *step_count;
+    int32_t stream;   /* ORC_STREAM_* */
+    uint64_t ph_step; /* fast stream: the launch-step counter */
 } nv_t;
 
 void *orc_nv_create(const orc_nv_cfg *cfg, int64_t n) {
@@ -611,24 +776,44 @@ void orc_nv_destroy(void *p) {
 void orc_nv_seed(void *p, const uint32_t *words, const int32_t *nwords) {
     nv_t *h = (nv_t *)p;
     for (int64_t i = 0; i < h->n; i++) orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
+    h->ph_step = 0; /* an unmasked seed restarts the fast stream's counter */
 }
 
+/* seeds the envs with mask[i] != 0 only; the fast stream's counter stays */
+void orc_nv_seed_masked(void *p, const uint32_t *words, const int32_t *nwords, const uint8_t *mask) {
+    nv_t *h = (nv_t *)p;
+    for (int64_t i = 0; i < h->n; i++)
+        if (mask[i]) orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
+}
+
+/* Fast stream: the five uniforms come from draw stream RESET of the counter's
+ * value, which the call consumes (invsim_reset and a NEXT_STEP reset step
+ * alike).  mask NULL: every env. */
+void orc_nv_reset_masked(void *p, float *obs, const uint8_t *mask);
+void orc_nv_reset(void *p, float *obs) { orc_nv_reset_masked(p, obs, NULL); }
+
 /* newsvendor.py:100-123 */
-void orc_nv_reset(void *p, float *obs) {
+void orc_nv_reset_masked(void *p, float *obs, const uint8_t *mask) {
     nv_t *h = (nv_t *)p;
     const int O = h->c.lead_time + 5;
+    const uint64_t step = h->ph_step;
 #pragma omp parallel for schedule(static) num_threads(orc_threads)
     for (int64_t i = 0; i < h->n; i++) {
-        uint64_t *rng = h->rng + 4 * i;
+        if (mask && !mask[i]) {
+            if (obs) memcpy(obs + (int64_t)O * i, h->state + (int64_t)O * i, sizeof(float) * O);
+            continue;
+        }
+        orc_gen gen = gen_env(h->stream, h->rng + 4 * i, step), *g = &gen;
+        gen_sub(g, ORC_PHILOX_RESET);
         double *par = h->par + 5 * i;
-        double price = orc_next_double(rng) * h->c.p_max;
+        double price = gen_double(g) * h->c.p_max;
         if (!(price > 1)) price = 1; /* max(1, x) */
-        double cost = orc_next_double(rng) * price;
+        double cost = gen_double(g) * price;
         if (!(cost > 1)) cost = 1;
         double mn = (h->c.h_max < cost) ? h->c.h_max : cost; /* min(cost, h_max) */
-        double hh = orc_next_double(rng) * mn;
-        double kk = orc_next_double(rng) * h->c.k_max;
-        double mu = orc_next_double(rng) * h->c.mu_max;
+        double hh = gen_double(g) * mn;
+        double kk = gen_double(g) * h->c.k_max;
+        double mu = gen_double(g) * h->c.mu_max;
         par[0] = price;
         par[1] = cost;
         par[2] = hh;
@@ -640,6 +825,7 @@ void orc_nv_reset(void *p, float *obs) {
         h->step_count[i] = 0;
         if (obs) memcpy(obs + (int64_t)O * i, st, sizeof(float) * O);
     }
+    if (h->stream == ORC_STREAM_PHILOX) h->ph_step = step + 1;
 }
 
 void orc_nv_get_params(void *p, double *params) {
@@ -662,9 +848,10 @@ void orc_nv_step(void *p, const float *action, float *obs, double *reward, uint8
     const int L = h->c.lead_time;
     const int O = L + 5;
     const tv ZERO = tv_make(0.0, K_PY);
+    const uint64_t step = h->ph_step;
 #pragma omp parallel for schedule(static) num_threads(orc_threads)
     for (int64_t i = 0; i < h->n; i++) {
-        uint64_t *rng = h->rng + 4 * i;
+        orc_gen gen = gen_env(h->stream, h->rng + 4 * i, step), *g = &gen;
         const double *par = h->par + 5 * i;
         float *st = h->state + (int64_t)O * i;
         h->step_count[i] += 1;                                                     /* :127 */
@@ -674,7 +861,7 @@ void orc_nv_step(void *p, const float *action, float *obs, double *reward, uint8
         tv cap = tv_bin(tv_make(h->c.max_inventory, K_PY), tv_make((double)S5, K_F32), '-');
         tv m1 = (cap.v < oq.v) ? cap : oq;                                         /* min(oq, cap) */
         tv q = (m1.v > 0) ? m1 : ZERO;                                             /* :143 max(0, .) */
-        int64_t d = orc_poisson(rng, par[4]);                                      /* :146 */
+        int64_t d = poisson_c(g, par[4], NULL);                                    /* :146 */
         tv dv = tv_make((double)d, K_PY);
         tv sales = (dv.v < inv.v) ? dv : inv;                                      /* :149 min(inv, d) */
         tv price = tv_make(par[0], K_PY), cost = tv_make(par[1], K_PY);
@@ -697,6 +884,7 @@ void orc_nv_step(void *p, const float *action, float *obs, double *reward, uint8
         if (demand) demand[i] = d;
         if (obs) memcpy(obs + (int64_t)O * i, st, sizeof(float) * O);
     }
+    if (h->stream == ORC_STREAM_PHILOX) h->ph_step = step + 1; /* one counter value per launch step */
 }
 
 /* ======================================================================
@@ -714,6 +902,8 @@ typedef struct {
     uint64_t *rng;
     int64_t *I, *R, *B, *alog; /* per env histories */
     int32_t *period;
+    int32_t stream;   /* ORC_STREAM_* */
+    uint64_t ph_step; /* fast stream: the launch-step counter */
 } im_t;
 
 void *orc_im_create(const orc_im_cfg *cfg, int64_t n) {
@@ -774,6 +964,16 @@ void orc_im_seed(void *p, const uint32_t *words, const int32_t *nwords) {
         orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
         h->u32[2 * i] = 0;   /* a new Generator: has_uint32 = 0 */
     }
+    h->ph_step = 0; /* an unmasked seed restarts the fast stream's counter */
+}
+
+void orc_im_seed_masked(void *p, const uint32_t *words, const int32_t *nwords, const uint8_t *mask) {
+    im_t *h = (im_t *)p;
+    for (int64_t i = 0; i < h->n; i++) {
+        if (!mask[i]) continue;
+        orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
+        h->u32[2 * i] = 0;
+    }
 }
 
 /* _get_obs :354-391 */
@@ -826,9 +1026,13 @@ void orc_im_step(void *p, const int64_t *action, int64_t *obs, double *reward, u
                  int64_t *backlog_next) {
     im_t *h = (im_t *)p;
     const int m1 = h->m1, m = h->m;
+    const uint64_t step = h->ph_step;
 #pragma omp parallel for schedule(static) num_threads(orc_threads)
     for (int64_t i = 0; i < h->n; i++) {
-        uint64_t *rng = h->rng + 4 * i;
+        /* demand: draw stream 0; the fast stream carries no 32-bit half between steps */
+        orc_gen gen = gen_env(h->stream, h->rng + 4 * i, step), *g = &gen;
+        uint32_t nobuf[2] = {0, 0};
+        uint32_t *u32 = h->stream == ORC_STREAM_PHILOX ? nobuf : h->u32 + 2 * i;
         const int t = h->period[i];
         int64_t *I = h->I + (int64_t)i * (h->T + 1) * m1;
         int64_t *R = h->R + (int64_t)i * (h->T + 1) * m1;
@@ -856,13 +1060,13 @@ void orc_im_step(void *p, const int64_t *action, int64_t *obs, double *reward, u
         if (h->dist == 5)
             d = t < h->T ? h->user_D[t] : 0;                          /* :182 */
         else if (h->dist == 2)
-            d = orc_binomial(rng, h->dn, h->dp);                      /* :175 */
+            d = binomial_c(g, h->dn, h->dp, NULL);                    /* :175 */
         else if (h->dist == 3)
-            d = orc_integers(rng, h->u32 + 2 * i, h->dlow, h->dhigh + 1); /* :178 */
+            d = integers_c(g, u32, h->dlow, h->dhigh + 1, NULL);      /* :178 */
         else if (h->dist == 4)
-            d = orc_geometric(rng, h->dp);                            /* :181 */
+            d = geometric_c(g, h->dp, NULL);                          /* :181 */
         else
-            d = orc_poisson(rng, h->mu);                              /* :172 */
+            d = poisson_c(g, h->mu, NULL);                            /* :172 */
         if (d < 0) d = 0;                                             /* :280 */
         int64_t dfill = d;
         if (t >= 1) dfill = wadd(dfill, B[(int64_t)t * m + 0]);       /* :285-286 */
@@ -894,6 +1098,7 @@ void orc_im_step(void *p, const int64_t *action, int64_t *obs, double *reward, u
         if (ending_inventory) for (int j = 0; j < m1; j++) ending_inventory[(int64_t)i * m1 + j] = Icur[j];
         if (backlog_next) for (int j = 0; j < m; j++) backlog_next[(int64_t)i * m + j] = B[(int64_t)(t + 1) * m + j];
     }
+    if (h->stream == ORC_STREAM_PHILOX) h->ph_step = step + 1; /* one counter value per launch step */
 }
 
 /* ======================================================================
@@ -915,6 +1120,8 @@ typedef struct {
     uint32_t *u32; /* per env [2]: the bit generator's buffered 32-bit half (integers markets) */
     double *X, *Y, *R, *S, *U, *D;
     int32_t *period;
+    int32_t stream;   /* ORC_STREAM_* */
+    uint64_t ph_step; /* fast stream: the launch-step counter */
 } net_t;
 
 #define DUP(dst, src, cnt, ty)                                  \
@@ -998,6 +1205,16 @@ void orc_net_seed(void *p, const uint32_t *words, const int32_t *nwords) {
         orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
         h->u32[2 * i] = 0;   /* a new Generator: has_uint32 = 0 */
     }
+    h->ph_step = 0; /* an unmasked seed restarts the fast stream's counter */
+}
+
+void orc_net_seed_masked(void *p, const uint32_t *words, const int32_t *nwords, const uint8_t *mask) {
+    net_t *h = (net_t *)p;
+    for (int64_t i = 0; i < h->n; i++) {
+        if (!mask[i]) continue;
+        orc_seed_pcg64(words + 4 * i, nwords[i], h->rng + 4 * i);
+        h->u32[2 * i] = 0;
+    }
 }
 
 #define NX(h, i) ((h)->X + (int64_t)(i) * ((h)->T + 2) * (h)->J)
@@ -1057,9 +1274,13 @@ void orc_net_step(void *p, const float *action, float *obs, double *reward, uint
     const int J = h->J, EE = h->E, RL = h->RL;
     const int E = EE ? EE : 1, RLs = RL ? RL : 1, SL = h->E + h->RL + 1;
     double cons[64], arr[64], xb[64], prof[64];
+    const uint64_t step = h->ph_step;
 #pragma omp parallel for schedule(static) num_threads(orc_threads) private(cons, arr, xb, prof)
     for (int64_t i = 0; i < h->n; i++) {
-        uint64_t *rng = h->rng + 4 * i;
+        /* the fast stream carries no 32-bit half between steps (one per step, as the device's) */
+        orc_gen gen = gen_env(h->stream, h->rng + 4 * i, step), *g = &gen;
+        uint32_t nobuf[2] = {0, 0};
+        uint32_t *u32 = h->stream == ORC_STREAM_PHILOX ? nobuf : h->u32 + 2 * i;
         const int t = h->period[i];
         double *X = NX(h, i), *Y = NY(h, i), *R = NR(h, i), *S = NS(h, i), *U = NU(h, i), *D = ND(h, i);
         for (int j = 0; j < J; j++) cons[j] = 0.0, arr[j] = 0.0;
@@ -1107,6 +1328,7 @@ void orc_net_step(void *p, const float *action, float *obs, double *reward, uint
         for (int j = 0; j < J; j++) xb[j] = X[(int64_t)(t + 1) * J + j];
         for (int r = 0; r < RL; r++) {
             double dd;
+            gen_sub(g, (uint32_t)r); /* fast stream: market r draws from stream r, drawing or not */
             if (h->rl_user[r]) {
                 int idx = t < h->T - 1 ? t : h->T - 1;
                 dd = h->user_D[(int64_t)r * h->T + idx];
@@ -1115,10 +1337,10 @@ void orc_net_step(void *p, const float *action, float *obs, double *reward, uint
             } else {                                       /* max(0, int(round(f(**p)))) :263 */
                 int64_t pd;
                 switch (h->rl_dist[r]) {
-                    case 2: pd = orc_binomial(rng, h->rl_n[r], h->rl_dp[r]); break;
-                    case 3: pd = orc_integers(rng, h->u32 + 2 * i, h->rl_n[r], h->rl_high[r]); break;
-                    case 4: pd = orc_geometric(rng, h->rl_dp[r]); break;
-                    default: pd = orc_poisson(rng, h->rl_lam[r]);
+                    case 2: pd = binomial_c(g, h->rl_n[r], h->rl_dp[r], NULL); break;
+                    case 3: pd = integers_c(g, u32, h->rl_n[r], h->rl_high[r], NULL); break;
+                    case 4: pd = geometric_c(g, h->rl_dp[r], NULL); break;
+                    default: pd = poisson_c(g, h->rl_lam[r], NULL);
                 }
                 dd = (double)(pd > 0 ? pd : 0);
             }
@@ -1184,6 +1406,7 @@ void orc_net_step(void *p, const float *action, float *obs, double *reward, uint
         if (Yo) for (int e = 0; e < EE; e++) Yo[(int64_t)i * EE + e] = Y[(int64_t)(t + 1) * E + e];
         if (Po) for (int j = 0; j < J; j++) Po[(int64_t)i * J + j] = prof[j];
     }
+    if (h->stream == ORC_STREAM_PHILOX) h->ph_step = step + 1; /* one counter value per launch step */
 }
 
 /* ======================================================================
@@ -1204,3 +1427,20 @@ void orc_net_rng(void *p, uint64_t *out) {
     net_t *h = (net_t *)p;
     memcpy(out, h->rng, sizeof(uint64_t) * 4 * (size_t)h->n);
 }
+
+/* ======================================================================
+ * The demand stream of a handle and the fast stream's launch-step counter
+ * (include/invsim.h INVSIM_DEMAND_PHILOX: the counter rules)
+ * ==================================================================== */
+#define STREAM_API(fam, T)                                                              \
+    int orc_##fam##_set_stream(void *p, int32_t stream) {                               \
+        if (stream != ORC_STREAM_NUMPY && stream != ORC_STREAM_PHILOX) return -1;       \
+        ((T *)p)->stream = stream;                                                      \
+        return 0;                                                                       \
+    }                                                                                   \
+    uint64_t orc_##fam##_philox_step(void *p) { return ((T *)p)->ph_step; }             \
+    void orc_##fam##_set_philox_step(void *p, uint64_t s) { ((T *)p)->ph_step = s; }
+
+STREAM_API(nv, nv_t)
+STREAM_API(im, im_t)
+STREAM_API(net, net_t)

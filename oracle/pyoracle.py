@@ -55,7 +55,23 @@ def _lib():
     lib.orc_sum_f64.restype = C.c_double
     lib.orc_set_threads.argtypes = [C.c_int]
     lib.orc_max_threads.restype = C.c_int
+    lib.orc_philox_block.argtypes = [P, P, P]
+    lib.orc_philox_init.argtypes = [P, C.c_uint64]
+    lib.orc_philox_set_step.argtypes = [P, C.c_uint64]
+    lib.orc_philox_sub.argtypes = [P, C.c_uint32]
+    lib.orc_philox_next64.argtypes = [P]
+    lib.orc_philox_next64.restype = C.c_uint64
+    lib.orc_philox_next_double.argtypes = [P]
+    lib.orc_philox_next_double.restype = C.c_double
+    lib.orc_philox_dist_fill_counted.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int64, C.c_int64,
+                                                 C.c_double, P, C.c_int64, P]
+    lib.orc_nv_reset_masked.argtypes = [P, P, P]
     for fam in ("nv", "im", "net"):
+        getattr(lib, f"orc_{fam}_set_stream").argtypes = [P, C.c_int32]
+        getattr(lib, f"orc_{fam}_philox_step").argtypes = [P]
+        getattr(lib, f"orc_{fam}_philox_step").restype = C.c_uint64
+        getattr(lib, f"orc_{fam}_set_philox_step").argtypes = [P, C.c_uint64]
+        getattr(lib, f"orc_{fam}_seed_masked").argtypes = [P, P, P, P]
         getattr(lib, f"orc_{fam}_create").argtypes = [P, C.c_int64]
         getattr(lib, f"orc_{fam}_create").restype = P
         getattr(lib, f"orc_{fam}_destroy").argtypes = [P]
@@ -146,7 +162,8 @@ COUNTERS = ("int_const", "int_full32", "int32_draw", "int32_reject", "int64_draw
             "btpe_fproduct", "btpe_fproduct_reject", "btpe_step52", "btpe_quick_accept",
             "btpe_quick_reject", "btpe_four_log", "btpe_four_log_reject",
             "geom_search", "geom_inversion", "geom_clamp",
-            "zig_slow", "zig_tail", "zig_wedge_accept", "zig_wedge_reject")
+            "zig_slow", "zig_tail", "zig_wedge_accept", "zig_wedge_reject",
+            "pois_ptrs", "pois_ptrs_reject", "pois_mult", "pois_mult_odd")
 
 
 def dist_stream_counts(seed, dist, n, n_or_low=0, high=0, p=0.0, state=None, buf=None):
@@ -160,6 +177,61 @@ def dist_stream_counts(seed, dist, n, n_or_low=0, high=0, p=0.0, state=None, buf
     lib().orc_dist_fill_counted(_p(st), _p(buf), int(dist), int(n_or_low), int(high), float(p), _p(out), n,
                                 _p(cnt))
     return out, st, buf, dict(zip(COUNTERS, cnt.tolist()))
+
+
+# ---------------------------------------------------------------- the fast stream
+STREAMS = {"numpy": 0, "philox": 1}
+PHILOX_RESET = 0xFFFFFFFF
+
+
+def philox_block(ctr, key):
+    """Philox4x32-10 of the counter words (4) under the key words (2): 4 words."""
+    c = np.array(ctr, np.uint32)
+    k = np.array(key, np.uint32)
+    out = np.zeros(4, np.uint32)
+    lib().orc_philox_block(_p(c), _p(k), _p(out))
+    return [int(x) for x in out]
+
+
+class PhiloxStruct(C.Structure):
+    _fields_ = [("key", C.c_uint32 * 2), ("s0", C.c_uint32), ("s1", C.c_uint32), ("r", C.c_uint32),
+                ("j", C.c_uint32), ("hold", C.c_uint64), ("have", C.c_int32)]
+
+
+class PhiloxGen:
+    """The oracle's fast-stream generator (oracle.h orc_philox) under a 64-bit key."""
+
+    def __init__(self, key64):
+        self.g = PhiloxStruct()
+        lib().orc_philox_init(C.byref(self.g), int(key64))
+
+    def set_step(self, s):
+        lib().orc_philox_set_step(C.byref(self.g), int(s))
+
+    def sub(self, r):
+        lib().orc_philox_sub(C.byref(self.g), int(r))
+
+    def next64(self):
+        return int(lib().orc_philox_next64(C.byref(self.g)))
+
+    def next_double(self):
+        return float(lib().orc_philox_next_double(C.byref(self.g)))
+
+
+def philox_key(seed):
+    """The fast stream's key of the env seeded with `seed`: its PCG64 increment high word."""
+    return int(pcg64_init(seed)[2])
+
+
+def philox_stream_counts(seed, dist, n, step0=0, r=0, n_or_low=0, high=0, p=0.0):
+    """The fast stream's draws of the env seeded with `seed` at launch steps
+    step0 .. step0 + n - 1 of draw stream r (dist 1: poisson(p), 2-4 as
+    dist_stream) and the branches they took: (draws, {counter name: events})."""
+    out = np.zeros(n, np.int64)
+    cnt = np.zeros(len(COUNTERS), np.int64)
+    lib().orc_philox_dist_fill_counted(philox_key(seed), int(step0), int(r), int(dist), int(n_or_low), int(high),
+                                       float(p), _p(out), n, _p(cnt))
+    return out, dict(zip(COUNTERS, cnt.tolist()))
 
 
 def exponential_stream(seed, n):
@@ -204,10 +276,31 @@ class _Base:
             getattr(lib(), f"orc_{self.fam}_destroy")(h)
             self.h = None
 
-    def seed(self, seeds):
+    def seed(self, seeds, mask=None):
+        """Seed every env (the fast stream's counter restarts), or with `mask`
+        (bool [n]) the masked ones only (the counter stays)."""
         w, nw = seed_words(seeds)
         assert len(w) == self.n
-        getattr(lib(), f"orc_{self.fam}_seed")(self.h, _p(w), _p(nw))
+        if mask is None:
+            getattr(lib(), f"orc_{self.fam}_seed")(self.h, _p(w), _p(nw))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+            getattr(lib(), f"orc_{self.fam}_seed_masked")(self.h, _p(w), _p(nw), _p(m))
+
+    def set_demand_stream(self, name):
+        """"numpy" (the reference's) or "philox" (include/invsim.h INVSIM_DEMAND_PHILOX)"""
+        if getattr(lib(), f"orc_{self.fam}_set_stream")(self.h, STREAMS[name]) != 0:
+            raise ValueError(name)
+        self.demand_stream = name
+
+    @property
+    def philox_step(self):
+        """the fast stream's launch-step counter (oracle.h: who advances it)"""
+        return int(getattr(lib(), f"orc_{self.fam}_philox_step")(self.h))
+
+    @philox_step.setter
+    def philox_step(self, s):
+        getattr(lib(), f"orc_{self.fam}_set_philox_step")(self.h, int(s) & (2**64 - 1))
 
     def rng_state(self):
         """[n][4] uint64 (state hi, state lo, inc hi, inc lo) of every env's PCG64."""
@@ -251,7 +344,7 @@ class OracleNewsvendor(_Base):
     fam = "nv"
 
     def __init__(self, n, lead_time=5, max_inventory=4000, max_order_quantity=2000, step_limit=40,
-                 p_max=100.0, h_max=5.0, k_max=10.0, mu_max=200.0, gamma=1.0):
+                 p_max=100.0, h_max=5.0, k_max=10.0, mu_max=200.0, gamma=1.0, demand_stream="numpy"):
         self.n = n
         self.L = max(0, int(lead_time))
         self.obs_dim = self.L + 5
@@ -259,10 +352,13 @@ class OracleNewsvendor(_Base):
                          float(max_order_quantity), float(p_max), float(h_max), float(k_max),
                          float(mu_max))
         self.h = lib().orc_nv_create(C.byref(self.cfg), n)
+        self.set_demand_stream(demand_stream)
 
-    def reset(self):
+    def reset(self, mask=None):
+        """mask (bool [n]): only those envs; the others' obs rows are their current state"""
         obs = np.zeros((self.n, self.obs_dim), np.float32)
-        lib().orc_nv_reset(self.h, _p(obs))
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+        lib().orc_nv_reset_masked(self.h, _p(obs), _p(m))
         return obs
 
     def step(self, action):
@@ -288,7 +384,7 @@ class OracleInvMgmt(_Base):
     def __init__(self, n, periods=30, I0=(100, 150, 200), p=20, r=(15, 10, 7, 5),
                  k=(0.10, 0.075, 0.05, 0.025), h=(0.15, 0.10, 0.05), c=(100, 200, 230),
                  L=(1, 5, 10), backlog=True, dist=1, dist_param=None, alpha=0.97, user_D=None,
-                 env_config=None, **_ignored):
+                 env_config=None, demand_stream="numpy", **_ignored):
         kw = dict(periods=periods, I0=I0, p=p, r=r, k=k, h=h, c=c, L=L, backlog=backlog, dist=dist,
                   dist_param=dist_param if dist_param is not None else {"mu": 20}, alpha=alpha,
                   user_D=user_D)
@@ -318,6 +414,7 @@ class OracleInvMgmt(_Base):
                          int(dp["n"]) if dist == 2 else 0, float(dp["p"]) if dist in (2, 4) else 0.0,
                          int(dp["low"]) if dist == 3 else 0, int(dp["high"]) if dist == 3 else 0)
         self.h = lib().orc_im_create(C.byref(self.cfg), n)
+        self.set_demand_stream(demand_stream)
 
     def reset(self):
         obs = np.zeros((self.n, self.obs_dim), np.int64)
@@ -508,7 +605,8 @@ class OracleNet(_Base):
     callers pass the *effective* backlog flag here."""
     fam = "net"
 
-    def __init__(self, n, graph=None, num_periods=30, backlog=True, alpha=1.0, user_D=None, sample_path=None):
+    def __init__(self, n, graph=None, num_periods=30, backlog=True, alpha=1.0, user_D=None, sample_path=None,
+                 demand_stream="numpy"):
         # network_management.py:77 works on graph.copy(): a copy keeps node and successor
         # order but rebuilds each predecessor list in graph.edges() order, which is the
         # order the arrival and purchase-cost sums then run in (:516-523, :586-592)
@@ -527,6 +625,7 @@ class OracleNet(_Base):
                                                      "rl_high", "rl_dp")])
         self.h = lib().orc_net_create(C.byref(self.cfg), n)
         self.obs_dim = int(lib().orc_net_obs_dim(self.h))
+        self.set_demand_stream(demand_stream)
         self.act_dim = self.topo["E"]
 
     def reset(self):

@@ -21,9 +21,10 @@ numpy itself (tests/test_oracle.py).
    caller-supplied policies, and the generic Net kernel with a rejecting
    integers market in front of another market.
 3. The buffered half across a checkpoint taken while the lookahead cache is live.
-4. The fast stream (demand_stream="philox") has no oracle: a chi-square of
-   2e6 draws against the exact pmf; tests/test_oracle.py passes numpy's own
-   samplers through the same function.
+4. The fast stream (demand_stream="philox"): a chi-square of 2e6 draws
+   against the exact pmf; tests/test_oracle.py passes numpy's own samplers
+   through the same function.  (Its draws are compared bit for bit with the
+   oracle's restatement of the stream in tests/test_gpu_philox_oracle.py.)
 """
 import numpy as np
 import pytest

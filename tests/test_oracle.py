@@ -1,5 +1,7 @@
 """CPU: the oracle against the reference's golden vectors and against numpy
 (the third-party RNG the reference calls).  No GPU needed."""
+import os
+
 import numpy as np
 import pytest
 
@@ -384,3 +386,268 @@ def test_oracle_net_market_samplers_vs_numpy(oracle, fn, dp):
         gen = np.random.Generator(np.random.PCG64(np.random.SeedSequence(100 + i)))
         exp = [[max(0, int(round(getattr(gen, fn)(**dp)))) for _ in range(3)] for _ in range(T)]
         assert np.array_equal(D[i], np.array(exp, np.float64)), (fn, i)
+
+
+# ---------------------------------------------------------------- the fast demand stream (Philox4x32-10)
+def _random_blocks(n, seed=5):
+    g = np.random.default_rng(seed)
+    w = g.integers(0, 2**32, size=(n, 6), dtype=np.uint64)
+    w[:8] = [[0] * 6, [2**32 - 1] * 6, [2**32 - 1, 0, 0, 0, 0, 0], [0, 2**32 - 1, 0, 0, 0, 0],
+             [0, 0, 2**32 - 1, 2**32 - 1, 0, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 2**32 - 1, 0],
+             [0, 0, 0, 0, 0, 2**32 - 1]]
+    return [[int(x) for x in row] for row in w]
+
+
+def test_philox_block_known_answers_and_python_model(oracle):
+    """The oracle's C block function == tests/philox_model.py (Python ints) on
+    the Random123 known-answer inputs, whose outputs rocRAND's host ten_rounds
+    printed (philox_cases.KAT), and on 10 000 random (counter, key) pairs."""
+    import philox_cases
+    import philox_model
+    for ctr, key, exp in philox_cases.KAT:
+        assert tuple(philox_model.block(ctr, key)) == exp, (ctr, key)
+        assert tuple(oracle.philox_block(ctr, key)) == exp, (ctr, key)
+    for w in _random_blocks(10_000):
+        assert oracle.philox_block(w[:4], w[4:]) == philox_model.block(w[:4], w[4:]), w
+
+
+def test_philox_block_vs_rocrand_host(oracle, tmp_path):
+    """rocRAND's own philox4x32_10_engine::ten_rounds (the function the device
+    stream calls), compiled for and run on the host: the known answers and 2 000
+    random blocks against the oracle's block function.  No GPU."""
+    import shutil
+    import subprocess
+    import philox_cases
+    from conftest import ORACLE
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found: rocRAND's host block function cannot be built")
+    if not os.path.exists(os.path.join(rocm, "include", "rocrand", "rocrand_philox4x32_10.h")):
+        pytest.skip("rocrand/rocrand_philox4x32_10.h not found next to hipcc")
+    exe = tmp_path / "philox_rocrand_host"
+    subprocess.run([hipcc, "-O1", "--offload-host-only", "-o", str(exe), os.path.join(ORACLE, "philox_rocrand_host.cpp")],
+                   check=True, capture_output=True)
+    blocks = [list(c) + list(k) for c, k, _ in philox_cases.KAT] + _random_blocks(2000, seed=6)
+    text = "".join(" ".join(f"{x:x}" for x in w) + "\n" for w in blocks)
+    out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+    got = [[int(x, 16) for x in line.split()] for line in out if line]
+    assert len(got) == len(blocks)
+    for (_, _, exp), g in zip(philox_cases.KAT, got):
+        assert tuple(g) == exp
+    for w, g in zip(blocks, got):
+        assert oracle.philox_block(w[:4], w[4:]) == g, w
+
+
+def test_philox_generator_semantics(oracle):
+    """The C generator against philox_model.Gen on hand-built cases: the first
+    uniform of a draw is (x.y:x.x) >> 11 of block 0 of (key, step, r); the
+    second output is (x.w:x.z) of the same block; the third opens block 1 (a
+    PTRS rejection continues the same (step, r) sequence); sub() drops a held
+    half and restarts the block index; set_step keeps neither; the step's high
+    word is counter word 3 and the key's low half key word 0."""
+    import philox_model
+    key = 0x0123456789ABCDEF
+    step = (5 << 32) | 7
+    kw = (key & 0xFFFFFFFF, key >> 32)
+    assert kw == (0x89ABCDEF, 0x01234567)
+    b0 = philox_model.block((0, 3, 7, 5), kw)
+    b1 = philox_model.block((1, 3, 7, 5), kw)
+    g = oracle.PhiloxGen(key)
+    g.set_step(step)
+    g.sub(3)
+    assert g.next_double() == ((b0[1] << 32 | b0[0]) >> 11) * 2.0 ** -53
+    assert g.next64() == b0[3] << 32 | b0[2]
+    assert g.next64() == b1[1] << 32 | b1[0]          # one half of block 1 is now held
+    g.sub(3)
+    assert g.next64() == b0[1] << 32 | b0[0], "sub() restarts at block 0 and drops the held half"
+    g.sub(philox_model.RESET)
+    r0 = philox_model.block((0, 0xFFFFFFFF, 7, 5), kw)
+    assert g.next64() == r0[1] << 32 | r0[0]
+    g.set_step(step + 2**32)                          # the step's high word moves alone
+    g.sub(0)
+    h0 = philox_model.block((0, 0, 7, 6), kw)
+    assert g.next64() == h0[1] << 32 | h0[0]
+    # a longer walk with interleaved repositioning, against the model generator
+    m, g = philox_model.Gen(key), oracle.PhiloxGen(key)
+    rg = np.random.default_rng(1)
+    for _ in range(400):
+        op = int(rg.integers(0, 6))
+        if op == 0:
+            s = int(rg.integers(0, 2**63)) * 2 + int(rg.integers(0, 2))
+            m.set_step(s), g.set_step(s)
+            r = int(rg.integers(0, 2**32))
+            m.sub(r), g.sub(r)
+        elif op == 1:
+            r = int(rg.integers(0, 2**32))
+            m.sub(r), g.sub(r)
+        else:
+            assert m.next64() == g.next64()
+    assert m.next_double() == g.next_double()
+
+
+def _model_poisson(gen, lam):
+    """numpy's random_poisson on a philox_model.Gen, for lam where no PTRS log test is needed to tell
+    the uniform count: the multiplication branch (lam < 10)"""
+    import math
+    enlam, X, prod = math.exp(-lam), 0, 1.0
+    while True:
+        prod *= gen.next_double()
+        if prod > enlam:
+            X += 1
+        else:
+            return X
+
+
+def test_philox_env_streams_follow_the_model(oracle):
+    """The env oracles on the fast stream against the Python model: InvMgmt's
+    demand of launch step s is the draw of stream 0 at counter s; a Net market
+    r draws from stream r; the Newsvendor reset's uniforms come from stream
+    RESET of the counter's value, and the step after it uses the next one."""
+    import philox_model
+    n, seed = 5, 77
+    keys = [oracle.philox_key(seed + i) for i in range(n)]
+    im = oracle.OracleInvMgmt(n, dist_param={"mu": 4.5}, demand_stream="philox")
+    im.seed(range(seed, seed + n))
+    im.reset()
+    im.philox_step = 2**32 - 2
+    for k in range(4):
+        d = im.step(np.zeros((n, 3), np.int64), info=True)[3]["demand"]
+        for i in range(n):
+            g = philox_model.Gen(keys[i])
+            g.set_step(2**32 - 2 + k)
+            g.sub(0)
+            assert d[i] == _model_poisson(g, 4.5), (k, i)
+    assert im.philox_step == 2**32 + 2
+    nv = oracle.OracleNewsvendor(n, mu_max=9.0, demand_stream="philox")
+    nv.seed(range(seed, seed + n))
+    assert nv.philox_step == 0
+    nv.reset()
+    assert nv.philox_step == 1
+    mu = nv.params()[:, 4]
+    d = nv.step(np.zeros(n, np.float32))[3]
+    for i in range(n):
+        g = philox_model.Gen(keys[i])
+        g.set_step(0)
+        g.sub(philox_model.RESET)
+        u = [g.next_double() for _ in range(5)]
+        assert mu[i] == u[4] * 9.0
+        g.set_step(1)
+        g.sub(0)
+        assert d[i] == _model_poisson(g, mu[i])
+    from invsim.topology import custom_graph
+    gr = custom_graph()
+    for e in [e for e in gr.edges() if "L" not in gr.edges[e]]:
+        gr.edges[e]["dist_param"] = {"lam": 6.0}
+    net = oracle.OracleNet(n, graph=gr, demand_stream="philox")
+    net.seed(range(seed, seed + n))
+    net.reset()
+    net.philox_step = 11
+    D = net.step(np.zeros((n, net.act_dim), np.float32), info=True)[3]["D"]
+    for i in range(n):
+        for r in range(3):
+            g = philox_model.Gen(keys[i])
+            g.set_step(11)
+            g.sub(r)
+            assert D[i, r] == _model_poisson(g, 6.0), (i, r)
+
+
+def test_philox_streams_are_independent(oracle):
+    """Guards of the restatement against the defects it is there to catch: the
+    custom graph's three Poisson(20) markets differ pairwise in more than half
+    of 1 000 envs x 30 steps, and the Newsvendor reset's mu is not a function
+    of the first demand's block (stream 0 of the same counter value)."""
+    import philox_model
+    from invsim.topology import custom_graph
+    n, T = 1000, 30
+    net = oracle.OracleNet(n, graph=custom_graph(), demand_stream="philox")
+    net.seed(range(900, 900 + n))
+    net.reset()
+    a = np.zeros((n, net.act_dim), np.float32)
+    D = np.stack([net.step(a, info=True)[3]["D"] for _ in range(T)])
+    assert D.shape == (T, n, 3)
+    for p, q in ((0, 1), (0, 2), (1, 2)):
+        assert (D[..., p] != D[..., q]).mean() > 0.5, (p, q)
+    assert (D[1:] != D[:-1]).mean() > 0.5, "consecutive launch steps draw from different blocks"
+    nv = oracle.OracleNewsvendor(n, demand_stream="philox")
+    nv.seed(range(900, 900 + n))
+    nv.reset()
+    mu = nv.params()[:, 4]
+    hits = 0
+    for i in range(n):
+        b = philox_model.block((0, 0, 0, 0), (lambda k: (k & 0xFFFFFFFF, k >> 32))(oracle.philox_key(900 + i)))
+        us = [((b[1] << 32 | b[0]) >> 11) * 2.0 ** -53, ((b[3] << 32 | b[2]) >> 11) * 2.0 ** -53]
+        hits += any(mu[i] == u * 200.0 for u in us)
+    assert hits == 0, "the reset's uniforms share the demand stream's block"
+
+
+@pytest.mark.parametrize("case", list(__import__("philox_cases").IM_CASES))
+def test_philox_gpu_cases_reach_their_branches(oracle, case):
+    """The floors of tests/test_gpu_philox_oracle.py, on the oracle's own draws
+    over exactly its seeds and launch steps: every Poisson case with lam >= 10
+    has >= 100 PTRS rejections (blocks j >= 1 are drawn), every multiplication
+    case >= 100 draws with an odd number of uniforms (a held half is dropped),
+    the integers case runs the 32-bit path and its rejection loop, and the
+    binomial / geometric ones BTPE's Step 52 and the ziggurat's slow path."""
+    import philox_cases
+    cnt = philox_cases.im_counts(case)
+    print(case, {k: v for k, v in cnt.items() if v})
+    for name in philox_cases.IM_FLOORS[case]:
+        assert cnt[name] >= philox_cases.FLOOR, (case, name, cnt[name])
+    if case == "int_0_3x2p30":
+        assert cnt["int64_draw"] == 0
+
+
+def test_philox_newsvendor_case_reaches_both_branches(oracle):
+    """The (L 2, limit 12, mu_max 14) Newsvendor case of the GPU test: over its
+    seeds, at least 100 episodes on each Poisson branch already at the first
+    reset (mu < 10: multiplication, mu >= 10: PTRS)."""
+    import philox_cases
+    (L, limit, mu_max), seed = philox_cases.NV_CASES["L2_mu14"]
+    n = philox_cases.N_ENV
+    nv = oracle.OracleNewsvendor(n, lead_time=L, step_limit=limit, mu_max=mu_max, demand_stream="philox")
+    nv.seed(range(seed, seed + n))
+    nv.reset()
+    mu = nv.params()[:, 4]
+    print("episodes with mu < 10:", int((mu < 10).sum()), " mu >= 10:", int((mu >= 10).sum()))
+    assert (mu < 10).sum() >= philox_cases.FLOOR and (mu >= 10).sum() >= philox_cases.FLOOR
+
+
+def test_numpy_stream_untouched_by_stream_api(oracle):
+    """set_demand_stream("philox") steps leave the PCG64 states alone, and a
+    handle switched back continues numpy's stream where it stood."""
+    n = 50
+    a = np.full((n, 3), 7, np.int64)
+    x = oracle.OracleInvMgmt(n, dist=3, dist_param={"low": 0, "high": 3 * 2**30})
+    y = oracle.OracleInvMgmt(n, dist=3, dist_param={"low": 0, "high": 3 * 2**30})
+    for o in (x, y):
+        o.seed(range(3, 3 + n))
+        o.reset()
+    for _ in range(3):
+        x.step(a), y.step(a)
+    st = x.rng_state().copy()
+    x.set_demand_stream("philox")
+    for _ in range(4):
+        x.step(a)
+    assert np.array_equal(x.rng_state(), st) and x.philox_step == 4
+    x.set_demand_stream("numpy")
+    for _ in range(5):
+        ox, oy = x.step(a, info=True), y.step(a, info=True)
+        assert np.array_equal(ox[3]["demand"], oy[3]["demand"])
+    assert np.array_equal(x.rng_state(), y.rng_state())
+
+
+@pytest.mark.parametrize("graph,markets", [("default", 1), ("custom", 3)])
+def test_philox_net_cases_reach_ptrs_rejections(oracle, graph, markets):
+    """The Net cases of the GPU test (Poisson(20) markets, draw stream r per
+    market): at least 100 PTRS rejections on every stream over its seeds and
+    the 78 launch steps of the step + rollout drive."""
+    import philox_cases
+    seed = philox_cases.NET_SEED[graph]
+    for r in range(markets):
+        rej = 0
+        for i in range(philox_cases.N_ENV):
+            _, cnt = oracle.philox_stream_counts(seed + i, 1, philox_cases.IM_STEPS, 0, r, p=20.0)
+            rej += cnt["pois_ptrs_reject"]
+        print(graph, "stream", r, "PTRS rejections:", rej)
+        assert rej >= philox_cases.FLOOR
