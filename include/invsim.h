@@ -214,6 +214,10 @@ int invsim_status(invsim_handle *h, uint32_t *flags, int32_t clear);
  *   INVSIM_POLICY_LEVELS       BaseStockAgent's rule with per-env, per-stage order-up-to levels
  *                              (and optional reorder points) from attached device arrays
  *                              (InvMgmt): see "Per-env base-stock levels" below
+ *   INVSIM_POLICY_NET_LEVELS   installation base-stock on a supply network: every reorder link
+ *                              orders up to its own per-env level against its purchaser's
+ *                              inventory position (NetInvMgmt, any graph): see "Per-env
+ *                              order-up-to levels on a supply network" below
  * CLASSIC_NV / SS need mu_max * (lead_time + 1) * max(1, safety_factor) <= 1e6 (INVSIM_ERANGE).
  * Per-env metrics (f64, accumulated with += so a caller may chain launches),
  * the sums evaluate_agent keeps (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -226,7 +230,7 @@ int invsim_status(invsim_handle *h, uint32_t *flags, int32_t clear);
  *   Newsvendor: [0], [1] only
  * Unavailable with SAME_STEP autoreset.  On NetInvMgmt graphs other than the
  * reference's default / custom ones (invsim_kernel_variant == 0) the agents
- * are CONSTANT and RANDOM. */
+ * are CONSTANT, RANDOM and NET_LEVELS. */
 #define INVSIM_POLICY_CONSTANT 1
 #define INVSIM_POLICY_BASE_STOCK 2
 #define INVSIM_POLICY_ORDER_UP_TO 3
@@ -243,7 +247,8 @@ typedef struct {
     const void *constant;    /* CONSTANT: host array [action_dim] in the action dtype: the action.
                               * RANDOM: host array [action_dim] in the action dtype: the action
                               * space's upper bounds `high` (the field's second use).
-                              * Both: action_dim <= INVSIM_POLICY_MAX_ACTION (INVSIM_ERANGE) */
+                              * NET_LEVELS: the same f32 upper bounds `high`.
+                              * All: action_dim <= INVSIM_POLICY_MAX_ACTION (INVSIM_ERANGE) */
 } invsim_policy;
 
 int invsim_metrics_dim(const invsim_handle *h, int32_t *dim);
@@ -457,6 +462,53 @@ int invsim_sample_actions(invsim_handle *h, int32_t K, const void *high, void *a
  * the one-wave run kernel otherwise). */
 #define INVSIM_POLICY_LEVELS 7
 int invsim_set_policy_levels(invsim_handle *h, const double *levels, const double *reorder);
+
+/* ---- Per-env order-up-to levels on a supply network (INVSIM_POLICY_NET_LEVELS;
+ * NetInvMgmt handles only, any graph).  The reference's NetInvMgmt scripts ship
+ * RandomAgent and ConstantOrderAgent only; the classical baseline on a network is
+ * an installation base-stock policy: every reorder link orders up to a level of
+ * its own against the inventory position of the node that buys over it.  The
+ * levels (and optional reorder points) of every env and link are read from a
+ * device array, so one launch scores N candidate vectors.
+ *
+ * invsim_set_policy_net_levels attaches `levels`, and optionally `reorder`, to h:
+ * device f64 [N][action_dim] (link k in the handle's reorder-link order),
+ * caller-owned, not copied, read by every NET_LEVELS launch at the time it runs
+ * (rewritable on the same stream between launches and between replays of a
+ * captured graph).  NULL levels detaches both.  Not during capture, and not on
+ * another family's handle (INVSIM_EINVAL).  INVSIM_POLICY_LEVELS and
+ * invsim_set_policy_levels stay InvMgmt's and refuse a NetInvMgmt handle.
+ *
+ * invsim_rollout_policy with kind = INVSIM_POLICY_NET_LEVELS: `constant` carries
+ * the host f32 [action_dim] upper bounds `high` of the action space (its use
+ * under RANDOM); safety_factor, mu and variant are ignored.  action_dim >
+ * INVSIM_POLICY_MAX_ACTION returns INVSIM_ERANGE; another family's handle, a NULL
+ * `constant` or nothing attached INVSIM_EINVAL.  For env n and reorder link k
+ * with purchaser p = pur[k], an applied step of period t computes, from the
+ * state at the start of the period (no order of this step placed yet; all links
+ * from the same state), bit for bit:
+ *   pos = X[t][p]                                                     f64
+ *   for k' = 0 .. E-1 ascending, if pur[k'] == p:   pos = pos + Y[t][k']
+ *   for r  = 0 .. RL-1 ascending, if rl_node[r] == p: pos = pos - U[t][r]
+ *   x = levels[n][k] - pos
+ *   with reorder: if not (pos < reorder[n][k]) then x = 0   (strict <; a NaN
+ *                 reorder point never orders)
+ *   x = x > 0 ? x : 0                               (a NaN level orders 0)
+ *   x = x > (double)high[k] ? (double)high[k] : x
+ *   action[k] = (float)x                            (f64 -> f32, round to nearest even)
+ * Plain f64 adds and subtracts in exactly that order (factory yields below 1
+ * make X fractional, so the order of the sum shows in the bits).  The step then
+ * treats `action` as any caller's action (rint, max(0, .)).  Everything else is
+ * CONSTANT's on NetInvMgmt: `actions` records the order of every stepped env, a
+ * NEXT_STEP reset step leaves its row unwritten and adds nothing to the metrics
+ * (same columns, same += order), SAME_STEP is refused, and the horizon refusal,
+ * the episode sink, the capture bracket, both demand streams, every market
+ * `dist` and user_D, lock-step and per-env periods and every graph are
+ * unchanged.  It runs on the launch paths CONSTANT has: the fused 3-role rollout
+ * and the one-wave specialised kernel on the reference's two graphs, the
+ * table-walking kernel on any other. */
+#define INVSIM_POLICY_NET_LEVELS 8
+int invsim_set_policy_net_levels(invsim_handle *h, const double *levels, const double *reorder);
 
 /* Episodic-return statistics of K steps of outputs, the reduction the
  * reference's evaluation harness keeps per episode (episode_rewards ->

@@ -84,7 +84,8 @@ struct invsim_handle {
     int64_t cap_steps = 0;
     // RandomAgent's action generators (invsim_set_action_rng): caller-owned u64 [4][Npad], or null
     uint64_t *arng = nullptr;
-    // the LEVELS policy's per-env parameters (invsim_set_policy_levels): caller-owned f64 [N][action_dim], or null
+    // the LEVELS policy's per-env parameters (invsim_set_policy_levels; on a NetInvMgmt handle NET_LEVELS',
+    // invsim_set_policy_net_levels): caller-owned f64 [N][action_dim], or null
     const double *levels = nullptr, *reorder = nullptr;
     std::string err;
 };
@@ -1214,6 +1215,21 @@ int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *poli
             p.levels = h->levels;       // safety_factor / mu are ignored: their slots hold the two pointers
             p.reorder = h->reorder;
             break;
+        case INVSIM_POLICY_NET_LEVELS:
+            if (h->family != INVSIM_NETINVMGMT) return fail(h, INVSIM_EINVAL, "NET_LEVELS is a NetInvMgmt policy");
+            if (!policy->constant) return fail(h, INVSIM_EINVAL, "NET_LEVELS policy needs the action space's upper bounds");
+            if (h->act_dim > POL_MAX_A) return fail(h, INVSIM_ERANGE, "action_dim too large for a NET_LEVELS policy");
+            if (!h->net_spec && net_random_lds_bytes(h->net) > 160 * 1024)
+                return fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch of a NET_LEVELS policy rollout "
+                                              "(the generic kernel keeps the orders of 64 envs in LDS)");
+            if (!h->levels)
+                return fail(h, INVSIM_EINVAL, "no levels attached: attach a device f64 [N][action_dim] array with "
+                                              "invsim_set_policy_net_levels");
+            p.kind = POL_NET_LEVELS;
+            p.levels = h->levels;       // safety_factor / mu are ignored: their slots hold the two pointers
+            p.reorder = h->reorder;
+            for (int a = 0; a < h->act_dim; a++) p.cf[a] = ((const float *)policy->constant)[a];
+            break;
         default: return fail(h, INVSIM_EINVAL, "unknown policy kind");
     }
     DeviceGuard g(h->device);
@@ -1452,6 +1468,15 @@ int invsim_set_policy_levels(invsim_handle *h, const double *levels, const doubl
     if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
     if (int rc = refuse_in_capture(h, "set_policy_levels")) return rc;
     if (h->family != INVSIM_INVMGMT) return fail(h, INVSIM_EINVAL, "LEVELS is an InvMgmt policy");
+    h->levels = levels;
+    h->reorder = levels ? reorder : nullptr;
+    return INVSIM_OK;
+}
+
+int invsim_set_policy_net_levels(invsim_handle *h, const double *levels, const double *reorder) {
+    if (!h) return fail(nullptr, INVSIM_EINVAL, "null handle");
+    if (int rc = refuse_in_capture(h, "set_policy_net_levels")) return rc;
+    if (h->family != INVSIM_NETINVMGMT) return fail(h, INVSIM_EINVAL, "NET_LEVELS is a NetInvMgmt policy");
     h->levels = levels;
     h->reorder = levels ? reorder : nullptr;
     return INVSIM_OK;

@@ -398,7 +398,7 @@ struct StepIO {
 // argument; for InvMgmt the translation unit invmgmt_ext.hip, INVSIM_IM_EXT_TU),
 // so no existing instantiation gains a branch.
 enum { POL_NONE = 0, POL_CONSTANT = 1, POL_BASE_STOCK = 2, POL_ORDER_UP_TO = 3, POL_CLASSIC_NV = 4,
-       POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7, POL_LEVELS = 8 };
+       POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7, POL_LEVELS = 8, POL_NET_LEVELS = 9 };
 constexpr int POL_MAX_A = 32;
 struct PolicyIO {
     int32_t kind;
@@ -407,15 +407,15 @@ struct PolicyIO {
     int32_t pad_;
     union {                   // (one slot, as below)
         double sf;            // safety factor (SS: S_buffer_factor)
-        const double *reorder;  // LEVELS: per-env reorder points [N][action_dim], or null
+        const double *reorder;  // LEVELS / NET_LEVELS: per-env reorder points [N][action_dim], or null
     };
     union {                   // (one slot: the struct keeps the size every policy kernel's arguments had)
         double mu;            // BASE_STOCK: demand mean
         uint64_t *arng;       // RANDOM: the action generators [4][Npad] (act_rng_rows)
-        const double *levels; // LEVELS: per-env order-up-to levels [N][action_dim]
+        const double *levels; // LEVELS / NET_LEVELS: per-env order-up-to levels [N][action_dim]
     };
     int64_t ci[POL_MAX_A];    // CONSTANT actions (RANDOM: the upper bounds), int64 action spaces
-    float cf[POL_MAX_A];      // CONSTANT actions (RANDOM: the upper bounds), f32 action spaces
+    float cf[POL_MAX_A];      // CONSTANT actions (RANDOM and NET_LEVELS: the upper bounds), f32 action spaces
     void *act_out;            // [K][N][action_dim] actions taken, may be null
     double *metrics;          // [N][mdim], accumulated (+=), may be null
 };
@@ -440,6 +440,23 @@ struct ActGen {
         act_rng_rows(pol.arng, npad).store_state(e, g);
     }
 };
+
+// NET_LEVELS (include/invsim.h, "Per-env order-up-to levels on a supply
+// network") is a compile-time variant, LVL, of the NetInvMgmt policy kernels (a
+// trailing template argument, so no other instantiation gains a branch or a
+// register).  One link's order from its purchaser's inventory position `pos`
+// (X + the pipelines into the node - the backlog of its markets, summed by the
+// caller in the contract's order); `reorder` is +inf when no reorder points are
+// attached, which orders exactly as the rule without them does: pos < +inf
+// holds for every finite and -inf pos, and a +inf or NaN pos orders 0 either way.
+__device__ __forceinline__ float net_level_order(double level, double reorder, double pos, float high) {
+    double x = level - pos;
+    if (!(pos < reorder)) x = 0.0;                 // strict <; a NaN reorder point never orders
+    x = x > 0 ? x : 0.0;                           // a NaN level orders 0
+    const double hi = (double)high;
+    x = x > hi ? hi : x;
+    return (float)x;                               // round to nearest even
+}
 
 // Lock-step period: when every env of the handle is at the same period the host
 // knows it (t_u >= 0) and the kernels neither read nor write the per-env
@@ -704,10 +721,10 @@ hipError_t net_spec_launch(int which, const NetParams &p, int t_u, const PolicyI
                            const StepIO<float, float> &io, bool &ahead, int &slot, hipStream_t s);
 hipError_t net_commit_launch(const NetParams &p, int slot, hipStream_t s);
 hipError_t net_reset_launch(const NetParams &p, const uint8_t *mask, float *obs, hipStream_t s);
-// generic (table-walking) kernel; pol: CONSTANT / RANDOM / EXTERNAL policy rollouts, or null
+// generic (table-walking) kernel; pol: CONSTANT / RANDOM / EXTERNAL / NET_LEVELS policy rollouts, or null
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
                           hipStream_t s);
 size_t net_lds_bytes(const NetParams &p);
-size_t net_random_lds_bytes(const NetParams &p);   // net_run_kernel's RANDOM variant
+size_t net_random_lds_bytes(const NetParams &p);   // net_run_kernel's RANDOM and NET_LEVELS variants
 
 }  // namespace invsim

@@ -219,7 +219,10 @@ __device__ bool net_step_lds(const NetParams &P, int64_t e, int gl, int t, RG &g
 // its action row.
 // EXT (POL_EXTERNAL, invsim_rollout_metrics): the policy bookkeeping with the
 // caller's action rows (io.act), as the open-loop path reads them.
-template <bool TU, bool POL, class RG, bool RND = false, bool EXT = false>
+// LVL (POL_NET_LEVELS, kernels.hpp net_level_order): every applied step writes
+// the env's orders, each link's from its purchaser's position in the X, U and Y
+// rows as they stand before the step, into the same LDS action row.
+template <bool TU, bool POL, class RG, bool RND = false, bool EXT = false, bool LVL = false>
 __global__ void __launch_bounds__(WAVE)
 net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) double net_lds[];
@@ -282,7 +285,21 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             } else {
                 double r;
                 if (RG::kCounter) u32 = 0;          // fast stream: no half carried between steps
-                tr = net_step_lds(P, e, gl, t, g, u32, s, RND ? arow : (POL && !EXT) ? pol.cf : io.act + oi * P.E, trow, r,
+                if constexpr (LVL) {
+                    for (int q = 0; q < P.E; q++) {
+                        const int p = P.pur[q];
+                        double pos = LV(s.X, p);
+                        for (int k2 = 0; k2 < P.E; k2++)
+                            if (P.pur[k2] == p) pos = pos + LV(s.Y, k2);
+                        for (int r2 = 0; r2 < P.RL; r2++)
+                            if (P.rl_node[r2] == p) pos = pos - LV(s.U, r2);
+                        const float a = net_level_order(pol.levels[e * P.E + q],
+                                                        pol.reorder ? pol.reorder[e * P.E + q] : __builtin_inf(), pos, pol.cf[q]);
+                        arow[q] = a;      // (as RND: the lane's own row)
+                        if (leader && pol.act_out) ((float *)pol.act_out)[oi * P.E + q] = a;
+                    }
+                }
+                tr = net_step_lds(P, e, gl, t, g, u32, s, (RND || LVL) ? arow : (POL && !EXT) ? pol.cf : io.act + oi * P.E, trow, r,
                                   k == io.K - 1 ? P.cm.info_demand : nullptr,
                                   k == io.K - 1 ? (double *)P.cm.info_rec : nullptr);
                 if (leader && (!POL || io.rew)) {
@@ -291,7 +308,7 @@ net_run_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
                     io.trunc[oi] = tr ? 1 : 0;
                 }
                 if (POL && leader) {
-                    if (!RND && !EXT && pol.act_out)
+                    if (!RND && !EXT && !LVL && pol.act_out)
                         for (int q = 0; q < P.E; q++) ((float *)pol.act_out)[oi * P.E + q] = pol.cf[q];
                     if (pol.metrics) {   // evaluate_agent metrics (benchmark_NetInvMgmtLostSalesEnv.py:264-300)
                         double *met = pol.metrics + e * (5 + P.J);
@@ -366,7 +383,7 @@ inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / b
 size_t net_lds_bytes(const NetParams &p) {
     return (size_t)scratch_rows(p.J, p.E, p.RL) * WAVE * sizeof(double) + net_tile_bytes(p);
 }
-// the RND variant's: + action rows [EPW][E] f32 behind the obs tile
+// the RND and LVL variants': + action rows [EPW][E] f32 behind the obs tile
 size_t net_random_lds_bytes(const NetParams &p) { return net_lds_bytes(p) + (size_t)EPW * p.E * sizeof(float); }
 
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
@@ -377,8 +394,22 @@ hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, cons
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
     PolicyIO none{};
     const PolicyIO &pv = pol ? *pol : none;
-    if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM && pol->kind != POL_EXTERNAL)
+    if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM && pol->kind != POL_EXTERNAL &&
+        pol->kind != POL_NET_LEVELS)
         return hipErrorInvalidValue;
+    if (pol && pol->kind == POL_NET_LEVELS) {
+        const size_t ldr = net_random_lds_bytes(p);          // the same action rows as RANDOM's
+        if (ldr > 160 * 1024 || !pol->levels) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses both first)
+#define KL_(TU)                                                                                        \
+    do {                                                                                               \
+        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, false, false, true>), grid, block, ldr, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, false, false, true>), grid, block, ldr, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KL_(true);
+        else KL_(false);
+#undef KL_
+        return hipGetLastError();
+    }
     if (pol && pol->kind == POL_EXTERNAL) {
 #define KE_(TU)                                                                                        \
     do {                                                                                               \

@@ -296,11 +296,44 @@ __device__ __forceinline__ void spec_shift(NetSt<G, RG> &s, const double (&Rn)[G
     }
 }
 
+// NET_LEVELS (kernels.hpp net_level_order): the env's levels and reorder points,
+// loaded once per launch and held in registers (+inf: no reorder points), and
+// the orders of one applied step from the state before it.  The position of a
+// node is X, plus the pipelines of the links into it in link order, minus the
+// backlog of its markets in retail-link order: plain f64 adds in that order.
+template <class G>
+struct NetLvl {
+    double lv[G::E], ro[G::E];
+    __device__ __forceinline__ void load(const PolicyIO &pol, int64_t el) {
+#pragma unroll
+        for (int k = 0; k < G::E; k++) lv[k] = pol.levels[el * G::E + k];
+#pragma unroll
+        for (int k = 0; k < G::E; k++) ro[k] = pol.reorder ? pol.reorder[el * G::E + k] : __builtin_inf();
+    }
+    template <class RG>
+    __device__ __forceinline__ void orders(const NetSt<G, RG> &s, const PolicyIO &pol, float (&act)[G::E]) const {
+        double pos[G::J];
+#pragma unroll
+        for (int j = 0; j < G::J; j++) {
+            pos[j] = s.X[j];
+#pragma unroll
+            for (int k = 0; k < G::E; k++)
+                if (G::pur[k] == j) pos[j] = pos[j] + s.Y[k];
+#pragma unroll
+            for (int r = 0; r < G::RL; r++)
+                if (G::rl_node[r] == j) pos[j] = pos[j] - s.U[r];
+        }
+#pragma unroll
+        for (int k = 0; k < G::E; k++) act[k] = net_level_order(lv[k], ro[k], pos[G::pur[k]], pol.cf[k]);
+    }
+};
+
 // RND (POL_RANDOM, kernels.hpp ActGen): the reorder quantities are drawn from
 // the env's action generator at the top of every launch step.
 // EXT (POL_EXTERNAL, invsim_rollout_metrics): the policy bookkeeping with the
 // caller's action rows (io.act), read as the open-loop path reads them.
-template <class G, bool TU, bool ONE, bool POL, class RG, bool RND = false, bool EXT = false>
+// LVL (POL_NET_LEVELS, NetLvl): every applied step orders from the state before it.
+template <class G, bool TU, bool ONE, bool POL, class RG, bool RND = false, bool EXT = false, bool LVL = false>
 __global__ void __launch_bounds__(WAVE)
 net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) float ns_lds[];
@@ -389,6 +422,8 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
     const int t_start = t;
     ActGen ag;
     if constexpr (RND) ag.load(pol, S, el);
+    NetLvl<G> lvl;
+    if constexpr (LVL) lvl.load(pol, el);
     double Rn[G::E];
 #pragma unroll
     for (int k = 0; k < G::E; k++) Rn[k] = 0.0;
@@ -430,6 +465,7 @@ net_spec_kernel(NetParams P, int t_u, StepIO<float, float> io, PolicyIO pol) {
             int64_t dem[G::RL];
             double *irec = (valid && kk == K - 1 && P.cm.info_rec)
                                ? (double *)P.cm.info_rec + e * (2 * G::RL + 2 * G::J + 2 * G::E) : nullptr;
+            if constexpr (LVL) lvl.orders(st, pol, act);
             const double r = spec_step<G>(P, pc, rhs_l, t, apow, st, act, trow, Rn, dem, POL ? met : nullptr, irec);
             tr = t + 1 >= P.T;
             if (POL) {
@@ -1150,7 +1186,10 @@ struct NetRoll3 {
 // RND (POL_RANDOM, kernels.hpp ActGen): the dynamics wave draws each launch
 // step's reorder quantities from the env's action generator, reset steps
 // included; the demand wave and its ring are as for ConstantOrder.
-template <class G, int CH_, bool POL, class RG = Pcg, bool RND = false>
+// LVL (POL_NET_LEVELS, NetLvl): the dynamics wave holds the env's levels and
+// reorder points in registers and computes every applied step's orders from
+// st.X, st.U and st.Y before the step; the other two waves are ConstantOrder's.
+template <class G, int CH_, bool POL, class RG = Pcg, bool RND = false, bool LVL = false>
 __global__ void __launch_bounds__(3 * WAVE)
 net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO pol) {
     using R3 = NetRoll3<G, CH_>;
@@ -1297,6 +1336,8 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
     double Rn[G::E];
     ActGen ag;
     if constexpr (RND) ag.load(pol, S, el);
+    NetLvl<G> lvl;
+    if constexpr (LVL) lvl.load(pol, el);
     net_wg_sync();   // barrier 0: demand chunk 0 ready
     for (int c = 0; c < nch; c++) {
         const double *db = dbuf + (c % RD) * CH * RL * WAVE;
@@ -1350,6 +1391,7 @@ net_roll3o_kernel(NetParams P, int t_start, StepIO<float, float> io, PolicyIO po
                     const double v = rg[(G::ring_off[q] + (int)((uint32_t)t % (uint32_t)G::L[q])) * WAVE];
                     wa[q] = (t >= G::L[q]) ? v : 0.0;
                 }
+                if constexpr (LVL) lvl.orders(st, pol, act);
                 const double rw = spec_core<G>(P, apow, st, act, Dd, wa, Rn, POL ? met : nullptr, nullptr);
                 if (POL) {
                     met[0] += rw;                                       // episode_reward += reward
@@ -1789,7 +1831,9 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
     } while (0)
     // ... and the in-kernel ConstantOrder agent on the 3-role kernel
     const bool rnd = pol && pol->kind == POL_RANDOM;
-    const bool pol_roll = pol && (pol->kind == POL_CONSTANT || rnd) && p.cm.kn.net_pol_roll;
+    const bool lvl = pol && pol->kind == POL_NET_LEVELS;
+    if (lvl && !pol->levels) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first)
+    const bool pol_roll = pol && (pol->kind == POL_CONSTANT || rnd || lvl) && p.cm.kn.net_pol_roll;
     if ((!pol || pol_roll) && io.K > 1 && t_u >= 0 && !p.cm.info_rec && p.cm.kn.net_roll &&
         (p.cm.autoreset == AR_NEXT_STEP || (p.cm.autoreset == AR_DISABLED && t_u + io.K <= p.T))) {
         const dim3 gr((unsigned)((p.cm.N + WAVE - 1) / WAVE));
@@ -1806,6 +1850,7 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
 #define RK_(RG)                                                                                                       \
     do {                                                                                                              \
         if (rnd) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG, true>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
+        else if (lvl) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG, false, true>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
         else if (pol) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
         else if (p.cm.kn.net_roll3) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, false, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
         else hipLaunchKernelGGL((net_roll_kernel<G, RG>), gr, dim3(2 * WAVE), NetRoll<G>::lds(), s, p, t_u, io);    \
@@ -1833,6 +1878,15 @@ static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, 
         if (t_u >= 0) KE_(true);
         else KE_(false);
 #undef KE_
+    } else if (lvl) {                               // the LVL variant: orders from the state before each step
+#define KL_(TU)                                                                                            \
+    do {                                                                                                   \
+        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, false, false, true>), grid, block, lds, s, p, t_u, io, pv); \
+        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, false, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
+    } while (0)
+        if (t_u >= 0) KL_(true);
+        else KL_(false);
+#undef KL_
     } else if (pol) {
         if (t_u >= 0) K_(true, false, true);
         else K_(false, false, true);

@@ -30,6 +30,7 @@ _LAZY = {
     "TorchPolicyAgent": "policies",
     "MLPPolicyAgent": "policies",
     "LevelsAgent": "policies",
+    "NetLevelsAgent": "policies",
     "evaluate_levels": "policies",
     "tune_levels": "policies",
     "convert_actions": "policies",

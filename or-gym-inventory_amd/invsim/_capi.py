@@ -32,7 +32,7 @@ EXPORTS = (
     "invsim_action_rng_bytes", "invsim_seed_action_rng", "invsim_set_action_rng", "invsim_sample_actions",
     "invsim_rollout_metrics",
     "invsim_mlp_create", "invsim_mlp_destroy", "invsim_mlp_actions", "invsim_rollout_mlp",
-    "invsim_set_policy_levels",
+    "invsim_set_policy_levels", "invsim_set_policy_net_levels",
 )
 ABI_VERSION = 4
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
@@ -67,7 +67,7 @@ class NetInvMgmtSpec(C.Structure):
 
 
 POLICY_KINDS = {"constant": 1, "base_stock": 2, "order_up_to": 3, "classic_nv": 4, "ss": 5, "random": 6,
-                "levels": 7}
+                "levels": 7, "net_levels": 8}
 
 
 class PolicySpec(C.Structure):
@@ -141,6 +141,7 @@ def _declare(lib):
         "invsim_mlp_actions": ([H, P, P, P, P, P], C.c_int),
         "invsim_rollout_mlp": ([H, I32, P, P, P, P, P, P, P, P, P], C.c_int),
         "invsim_set_policy_levels": ([H, P, P], C.c_int),
+        "invsim_set_policy_net_levels": ([H, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

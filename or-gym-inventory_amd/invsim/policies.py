@@ -29,6 +29,12 @@ Agents (restated from the reference, same names and constructor arguments):
   ``evaluate_levels`` scores ``[C, A]`` candidates on common seeds in one
   launch and ``tune_levels`` searches them (``include/invsim.h``, "Per-env
   base-stock levels")
+* ``NetLevelsAgent(levels, reorder)`` the same on a supply network: every
+  reorder link orders up to its own per-env level against its purchaser's
+  inventory position, NetInvMgmt envs and any graph; ``from_mean_demand``
+  derives levels from the topology, and ``evaluate_levels`` / ``tune_levels``
+  take NetInvMgmt env classes too (``include/invsim.h``, "Per-env order-up-to
+  levels on a supply network")
 
 Policies computed outside the kernels (a trained ``torch.nn.Module`` actor, the
 scripts' ``SB3AgentWrapper``: benchmark_InvManagementBacklogEnv.py:332-342) go
@@ -259,6 +265,102 @@ class LevelsAgent(_Agent):
         bufs = self.tensors(env)
         env._attach_policy_levels(*bufs)               # (kept alive by the env while attached)
         return _capi.PolicySpec(_capi.POLICY_KINDS["levels"], 0, 0.0, 0.0, None), bufs
+
+
+def _market_means(tp):
+    """Mean demand per period of every market link of a compiled topology:
+    poisson lam, binomial n p, integers the mean of numpy's half-open range,
+    geometric 1 / p, a user_D replay the mean of max(0, round(x))."""
+    t = tp.tables
+    out = np.zeros(len(tp.retail_links), np.float64)
+    for r in range(len(tp.retail_links)):
+        if t["rl_user"][r]:
+            out[r] = float(np.mean(np.maximum(0.0, np.rint(t["user_D"][r]))))
+            continue
+        kind = int(t["rl_dist"][r])
+        if kind == 1:
+            out[r] = float(t["rl_lam"][r])
+        elif kind == 2:
+            out[r] = float(t["rl_n"][r]) * float(t["rl_dp"][r])
+        elif kind == 3:
+            out[r] = (float(t["rl_n"][r]) + float(t["rl_high"][r]) - 1.0) / 2.0
+        else:
+            out[r] = 1.0 / float(t["rl_dp"][r])
+    return out
+
+
+class NetLevelsAgent(LevelsAgent):
+    """Installation base-stock on a supply network (NetInvMgmt envs, any graph):
+    every reorder link ``k`` orders up to ``levels[n][k]`` against the inventory
+    position of the node that buys over it -- its on-hand ``X``, plus the
+    pipelines ``Y`` of every link into it, minus the backlog ``U`` of its
+    markets -- clipped to ``[0, action_space.high]``, and with ``reorder`` only
+    while that position is strictly below the link's reorder point
+    (``include/invsim.h``, "Per-env order-up-to levels on a supply network").
+    The tensors, what is used in place, captures and keep-alive are
+    ``LevelsAgent``'s; the kernels are the NetInvMgmt ones."""
+
+    def __init__(self, levels, reorder=None, name="NetLevels"):
+        super().__init__(levels, reorder, name)
+
+    @classmethod
+    def from_mean_demand(cls, env_or_topology, safety_factor=1.0, **kw):
+        """Levels that cover the mean demand over each link's lead time plus the
+        review period, ``safety_factor * (L_k + 1) * f[k]``, from the compiled
+        topology alone (host only).  ``d[j]``, the demand rate at node ``j``, is
+        the mean demand of its markets plus ``f[k] / v[j]`` over the links ``j``
+        supplies; a node splits its rate evenly over the links into it, ``f[k] =
+        d[pur[k]] / (links into pur[k])``; evaluated from the markets upstream."""
+        tp = getattr(env_or_topology, "topology", env_or_topology)
+        t = tp.tables
+        E, J = len(tp.reorder_links), len(tp.main_nodes)
+        pur, sup = t["pur"][:E], t["sup"][:E]
+        mkt = _market_means(tp)
+        n_in = np.bincount(pur, minlength=J)
+        d, f = [None] * J, [None] * E
+        busy = set()
+
+        def rate(j):
+            if d[j] is None:
+                if j in busy:
+                    raise ValueError("from_mean_demand needs an acyclic supply network")
+                busy.add(j)
+                x = 0.0
+                for r in range(len(tp.retail_links)):
+                    if t["rl_node"][r] == j:
+                        x += mkt[r]
+                for k in range(E):
+                    if sup[k] == j:
+                        x += flow(k) / float(t["v"][j])
+                busy.discard(j)
+                d[j] = x
+            return d[j]
+
+        def flow(k):
+            if f[k] is None:
+                f[k] = rate(int(pur[k])) / float(n_in[pur[k]])
+            return f[k]
+
+        lv = np.array([safety_factor * (float(t["L"][k]) + 1.0) * flow(k) for k in range(E)], np.float64)
+        return cls(lv, **kw)
+
+    def tensors(self, env):
+        """(levels, reorder or None): the float64 ``[N, A]`` device tensors the
+        kernels read for this agent on ``env`` (made at the first call)."""
+        if env.family != _capi.INVSIM_NETINVMGMT:
+            raise TypeError("NetLevelsAgent needs a NetInvMgmt env")
+        bufs = self._bufs.get(env)
+        if bufs is None:
+            bufs = (self._on_device(env, self.levels, "levels"),
+                    None if self.reorder is None else self._on_device(env, self.reorder, "reorder"))
+            self._bufs[env] = bufs
+        return bufs
+
+    def device_spec(self, env):
+        bufs = self.tensors(env)
+        env._attach_policy_levels(*bufs)               # (kept alive by the env while attached)
+        high = env._action_high()
+        return _capi.PolicySpec(_capi.POLICY_KINDS["net_levels"], 0, 0.0, 0.0, high.ctypes.data), (bufs, high)
 
 
 def convert_actions(raw, low, high, dtype):
@@ -684,10 +786,15 @@ def _levels_env(env_cls, env_config, n_cand, n_episodes, seed_offset, device):
     """One env of n_cand * n_episodes instances; instance c * n_episodes + r
     will run candidate c on seed seed_offset + r (the returned seed list)."""
     env = env_cls(num_envs=n_cand * n_episodes, device=device, autoreset_mode="disabled", **(env_config or {}))
-    if env.family != _capi.INVSIM_INVMGMT:
+    if env.family not in (_capi.INVSIM_INVMGMT, _capi.INVSIM_NETINVMGMT):
         env.close()
-        raise TypeError("level policies need an InvManagement env class")
+        raise TypeError("level policies need an InvManagement or NetInvMgmt env class")
     return env, [seed_offset + r for _ in range(n_cand) for r in range(n_episodes)]
+
+
+def _levels_agent_cls(env):
+    """the family's level policy: LevelsAgent (InvMgmt) or NetLevelsAgent (NetInvMgmt)"""
+    return NetLevelsAgent if env.family == _capi.INVSIM_NETINVMGMT else LevelsAgent
 
 
 def _levels_columns(family, met, n_cand, n_episodes):
@@ -713,7 +820,9 @@ def evaluate_levels(levels, env_cls, env_config=None, n_episodes=100, seed_offse
     ``evaluate_agent(LevelsAgent(levels[c]), ...)`` on the same seeds, bit for
     bit), and under ``"candidates"`` a dict of the per-candidate ``AvgReward``,
     ``StdReward``, ``AvgServiceLevel`` and ``AvgEndingInv``, each ``[C]`` (the
-    means of those rows; the per-episode columns keep the two shared names)."""
+    means of those rows; the per-episode columns keep the two shared names).
+    With a NetInvMgmt env class the candidates are ``NetLevelsAgent`` levels per
+    reorder link and the columns are that family's ``summarize`` columns."""
     rows = lambda a: np.repeat(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a,  # noqa: E731
                                           np.float64), n_episodes, axis=0)
     lv = rows(levels)
@@ -724,7 +833,7 @@ def evaluate_levels(levels, env_cls, env_config=None, n_episodes=100, seed_offse
     try:
         env.reset(seed=seeds)
         met = torch.zeros((env.num_envs, metrics_dim(env)), dtype=torch.float64, device=env.device)
-        agent = LevelsAgent(lv, None if reorder is None else rows(reorder))
+        agent = _levels_agent_cls(env)(lv, None if reorder is None else rows(reorder))
         rollout_policy(env, agent, env._horizon(), obs=False, rewards=False, metrics=met)
         return _levels_columns(env.family, met.cpu().numpy(), n_cand, n_episodes)
     finally:
@@ -746,7 +855,10 @@ def tune_levels(env_cls, env_config=None, n_episodes=64, population=256, iterati
     capacity ``c`` is out of reach.  Candidate 0 of every generation is the
     incumbent best (``init``, default the ``safety_factor = 1`` levels, in the
     first): the same seeds and levels give the same bits, so its score is
-    reproduced exactly and the best score never decreases.
+    reproduced exactly and the best score never decreases.  A NetInvMgmt env
+    class searches ``NetLevelsAgent`` levels per reorder link: ``init`` defaults
+    to ``NetLevelsAgent.from_mean_demand`` and ``max_level`` to the action
+    space's ``high``.
 
     Returns a dict: ``levels`` [A] the best vector, ``TotalReward``
     [n_episodes] its per-episode rewards, ``history`` [iterations] the best
@@ -756,16 +868,21 @@ def tune_levels(env_cls, env_config=None, n_episodes=64, population=256, iterati
     env, seeds = _levels_env(env_cls, env_config, population, n_episodes, seed_offset, device)
     try:
         A = env.action_dim
-        base = np.asarray((env.lead_time + 1) * env.dist_param.get("mu", 10), np.float64)
-        hi = np.maximum(3.0 * base, env.supply_capacity.astype(np.float64)) if max_level is None else \
-            np.broadcast_to(np.asarray(max_level, np.float64), (A,))
+        if env.family == _capi.INVSIM_NETINVMGMT:
+            base = np.asarray(NetLevelsAgent.from_mean_demand(env).levels, np.float64)
+            hi = env._action_high().astype(np.float64)
+        else:
+            base = np.asarray((env.lead_time + 1) * env.dist_param.get("mu", 10), np.float64)
+            hi = np.maximum(3.0 * base, env.supply_capacity.astype(np.float64))
+        if max_level is not None:
+            hi = np.broadcast_to(np.asarray(max_level, np.float64), (A,))
         hi = torch.from_numpy(np.ascontiguousarray(hi))
         best = torch.as_tensor(np.asarray(base if init is None else init, np.float64)).reshape(A).clone()
         mean, std = best.clone(), hi / 4
         gen = torch.Generator().manual_seed(int(seed))
         n_elite = max(2, int(round(elite_frac * population)))
         lv = torch.empty((env.num_envs, A), dtype=torch.float64, device=env.device)
-        agent = LevelsAgent(lv)
+        agent = _levels_agent_cls(env)(lv)
         met = torch.zeros((env.num_envs, metrics_dim(env)), dtype=torch.float64, device=env.device)
         history, best_rew = [], None
         for _ in range(iterations):

@@ -358,12 +358,17 @@ class InvSimVectorEnv:
 
     def _attach_policy_levels(self, levels, reorder=None):
         """Attach the LEVELS policy's device tensors (float64 [N, A]); they stay
-        alive here while attached.  Nothing to do when they already are."""
+        alive here while attached.  Nothing to do when they already are.  On a
+        NetInvMgmt env they are the NET_LEVELS policy's (a handle is of one
+        family, so one slot holds either)."""
         cur = self._levels
         if cur is not None and cur[0] is levels and cur[1] is reorder:
             return
         p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _capi.check(self._lib.invsim_set_policy_levels(self._h, p(levels), p(reorder)), self._h, "set_policy_levels")
+        net = self.family == _capi.INVSIM_NETINVMGMT
+        attach = self._lib.invsim_set_policy_net_levels if net else self._lib.invsim_set_policy_levels
+        _capi.check(attach(self._h, p(levels), p(reorder)), self._h,
+                    "set_policy_net_levels" if net else "set_policy_levels")
         self._levels = (levels, reorder) if levels is not None else None
 
     def seed_actions(self, seed):
