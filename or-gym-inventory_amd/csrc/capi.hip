@@ -13,6 +13,7 @@
 
 #include "../../include/invsim.h"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "mlp_policy.hpp"
 
 using namespace invsim;
@@ -52,8 +53,7 @@ struct invsim_handle {
     int64_t arena_bytes = 0;
     char *tables = nullptr;     // read-only tables (not part of the state blob)
     void *scratch = nullptr;    // caches derived from the state (not part of the blob)
-    bool la_valid = false;      // demand lookahead cache (Im/NvParams::ahead) is valid
-    int la_slot = 0;            //   ... with this current slot
+    Lookahead la;               // demand lookahead cache (Nv/Im/NetParams::ahead): valid, and its current slot
     std::vector<Field> fields;
     Common cm{};
     NvParams nv{};
@@ -78,9 +78,9 @@ struct invsim_handle {
     // graph capture (invsim_capture_begin / _end): the host-side position at
     // begin, put back at end, and the env steps the captured calls enqueue
     bool capturing = false;
-    bool cap_t_known = true, cap_la_valid = false;
+    bool cap_t_known = true;
     int32_t cap_t_cur = 0;
-    int cap_la_slot = 0;
+    Lookahead cap_la;
     int64_t cap_steps = 0;
     // RandomAgent's action generators (invsim_set_action_rng): caller-owned u64 [4][Npad], or null
     uint64_t *arng = nullptr;
@@ -739,7 +739,7 @@ int invsim_create_netinvmgmt(const invsim_netinvmgmt_spec *s, int64_t n, int32_t
         p.E = E;
         p.RL = RL;
         p.sumL = sumL;
-        if (net_lds_bytes(p) > 160 * 1024) rc = fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch");
+        if (net_lds_bytes(p) > LDS_LIMIT_BYTES) rc = fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch");
     }
     if (rc == INVSIM_OK) {
         NetParams &p = h->net;
@@ -874,11 +874,11 @@ int invsim_set_info_demand(invsim_handle *h, int64_t *demand) {
 // bring cm.rng up to date from the demand lookahead cache (the cache stays valid)
 static int commit_rng(invsim_handle *h, hipStream_t s) {
     // a fast-stream cache holds demands only (set_demand_stream drops the other kind)
-    if (!h->la_valid || h->demand_stream == INVSIM_DEMAND_PHILOX) return INVSIM_OK;
+    if (!h->la.valid || h->demand_stream == INVSIM_DEMAND_PHILOX) return INVSIM_OK;
     hipError_t e = hipSuccess;
-    if (h->family == INVSIM_INVMGMT) e = im_commit_launch(h->im, h->la_slot, s);
-    else if (h->family == INVSIM_NEWSVENDOR) e = nv_commit_launch(h->nv, h->la_slot, s);
-    else if (h->family == INVSIM_NETINVMGMT) e = net_commit_launch(h->net, h->la_slot, s);
+    if (h->family == INVSIM_INVMGMT) e = im_commit_launch(h->im, h->la.slot, s);
+    else if (h->family == INVSIM_NEWSVENDOR) e = nv_commit_launch(h->nv, h->la.slot, s);
+    else if (h->family == INVSIM_NETINVMGMT) e = net_commit_launch(h->net, h->la.slot, s);
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "rng commit");
 }
 
@@ -901,7 +901,7 @@ int invsim_seed_range(invsim_handle *h, uint64_t base_lo, uint64_t base_hi, int6
     DeviceGuard g(h->device);
     int rc = commit_rng(h, (hipStream_t)stream);   // a masked seed keeps the other streams
     if (rc != INVSIM_OK) return rc;
-    h->la_valid = false;   // the lookahead cache follows the old streams
+    h->la.valid = false;   // the lookahead cache follows the old streams
     if (!mask) ph_counter_restart(h);
     hipError_t e = seed_range_launch(h->cm, base_lo, base_hi, first, mask, (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "seed_range launch");
@@ -915,7 +915,7 @@ int invsim_seed_words(invsim_handle *h, const uint32_t *words, const int32_t *nw
     DeviceGuard g(h->device);
     int rc = commit_rng(h, (hipStream_t)stream);
     if (rc != INVSIM_OK) return rc;
-    h->la_valid = false;
+    h->la.valid = false;
     if (!mask) ph_counter_restart(h);
     hipError_t e = seed_words_launch(h->cm, words, nwords, mask, (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "seed_words launch");
@@ -943,7 +943,7 @@ int invsim_reset(invsim_handle *h, const uint8_t *mask, void *obs, void *stream)
     if (h->family == INVSIM_NEWSVENDOR) {   // its reset draws from cm.rng (or the fast stream)
         int rc = commit_rng(h, s);
         if (rc != INVSIM_OK) return rc;
-        h->la_valid = false;
+        h->la.valid = false;
         if (h->demand_stream == INVSIM_DEMAND_PHILOX) {
             rc = ph_counter_sync(h, s);
             if (rc != INVSIM_OK) return rc;
@@ -1018,25 +1018,25 @@ static int steps_launch(invsim_handle *h, int K, const void *actions, void *obs,
     switch (h->family) {
         case INVSIM_NEWSVENDOR: {
             StepIO<float, float> io{K, (const float *)actions, (float *)obs, reward, terminated, truncated, (float *)final_obs};
-            e = nv_run_launch(h->nv, t_u, pol, io, h->la_valid, h->la_slot, s);
+            e = nv_run_launch(h->nv, t_u, pol, io, h->la, s);
             break;
         }
         case INVSIM_INVMGMT: {
             StepIO<int64_t, int64_t> io{K, (const int64_t *)actions, (int64_t *)obs, reward, terminated, truncated,
                                         (int64_t *)final_obs};
-            e = im_run_launch(h->im, h->im_ap.data(), h->im_m1, h->im_backlog, t_u, pol, io, h->la_valid, h->la_slot, sunk, s);
+            e = im_run_launch(h->im, h->im_ap.data(), h->im_m1, h->im_backlog, t_u, pol, io, h->la, sunk, s);
             break;
         }
         case INVSIM_NETINVMGMT: {
             StepIO<float, float> io{K, (const float *)actions, (float *)obs, reward, terminated, truncated, (float *)final_obs};
-            e = h->net_spec ? net_spec_launch(h->net_spec, h->net, t_u, pol, io, h->la_valid, h->la_slot, s)
+            e = h->net_spec ? net_spec_launch(h->net_spec, h->net, t_u, pol, io, h->la, s)
                             : net_run_launch(h->net, t_u, pol, io, s);
             break;
         }
         default: return fail(h, INVSIM_EINVAL, "bad handle family");
     }
     if (e != hipSuccess) {
-        h->la_valid = false;
+        h->la.valid = false;
         return hip_fail(h, e, "step launch");
     }
     if (h->cm.ep_ret && !sunk) {
@@ -1142,7 +1142,7 @@ static PolicyIO external_policy(const invsim_handle *h, double *metrics) {
 static int random_policy(invsim_handle *h, const void *high, PolicyIO &p, bool rollout) {
     if (!high) return fail(h, INVSIM_EINVAL, "RANDOM policy needs the action space's upper bounds");
     if (h->act_dim > POL_MAX_A) return fail(h, INVSIM_ERANGE, "action_dim too large for a RANDOM policy");
-    if (rollout && h->family == INVSIM_NETINVMGMT && !h->net_spec && net_random_lds_bytes(h->net) > 160 * 1024)
+    if (rollout && h->family == INVSIM_NETINVMGMT && !h->net_spec && net_random_lds_bytes(h->net) > LDS_LIMIT_BYTES)
         return fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch of a RANDOM policy rollout "
                                       "(the generic kernel keeps the drawn actions of 64 envs in LDS)");
     if (!h->arng)
@@ -1219,7 +1219,7 @@ int invsim_rollout_policy(invsim_handle *h, int32_t K, const invsim_policy *poli
             if (h->family != INVSIM_NETINVMGMT) return fail(h, INVSIM_EINVAL, "NET_LEVELS is a NetInvMgmt policy");
             if (!policy->constant) return fail(h, INVSIM_EINVAL, "NET_LEVELS policy needs the action space's upper bounds");
             if (h->act_dim > POL_MAX_A) return fail(h, INVSIM_ERANGE, "action_dim too large for a NET_LEVELS policy");
-            if (!h->net_spec && net_random_lds_bytes(h->net) > 160 * 1024)
+            if (!h->net_spec && net_random_lds_bytes(h->net) > LDS_LIMIT_BYTES)
                 return fail(h, INVSIM_ERANGE, "topology too large for the LDS scratch of a NET_LEVELS policy rollout "
                                               "(the generic kernel keeps the orders of 64 envs in LDS)");
             if (!h->levels)
@@ -1567,7 +1567,7 @@ int invsim_set_demand_stream(invsim_handle *h, int32_t mode) {
     if (rc != INVSIM_OK) return rc;
     e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return hip_fail(h, e, "demand stream switch");
-    h->la_valid = false;
+    h->la.valid = false;
     h->demand_stream = mode;
     h->cm.philox = mode == INVSIM_DEMAND_PHILOX ? 1 : 0;
     sync_common(h);
@@ -1650,7 +1650,7 @@ int invsim_set_state(invsim_handle *h, const void *src, void *stream) {
                                   (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(h, e, "set_state");
     h->t_known = false;  // periods now come from the blob
-    h->la_valid = false;
+    h->la.valid = false;
     h->ph_from_blob = true;   // and the fast stream's counter (read when next needed)
     return INVSIM_OK;
 }
@@ -1665,8 +1665,7 @@ int invsim_capture_begin(invsim_handle *h) {
     h->capturing = true;
     h->cap_t_known = h->t_known;
     h->cap_t_cur = h->t_cur;
-    h->cap_la_valid = h->la_valid;
-    h->cap_la_slot = h->la_slot;
+    h->cap_la = h->la;
     h->cap_steps = 0;
     return INVSIM_OK;
 }
@@ -1676,19 +1675,18 @@ int invsim_capture_end(invsim_handle *h, int64_t *steps) {
     if (!h->capturing) return fail(h, INVSIM_EINVAL, "capture_end without capture_begin");
     if (steps) *steps = h->cap_steps;
     const bool closed = h->t_known == h->cap_t_known && (!h->t_known || h->t_cur == h->cap_t_cur) &&
-                        h->la_valid == h->cap_la_valid && (!h->la_valid || h->la_slot == h->cap_la_slot);
+                        h->la.valid == h->cap_la.valid && (!h->la.valid || h->la.slot == h->cap_la.slot);
     const int32_t t_end = h->t_known ? h->t_cur : -1;
-    const bool la_end = h->la_valid;
+    const bool la_end = h->la.valid;
     // nothing ran: the device is still where capture_begin found it
     h->capturing = false;
     h->t_known = h->cap_t_known;
     h->t_cur = h->cap_t_cur;
-    h->la_valid = h->cap_la_valid;
-    h->la_slot = h->cap_la_slot;
+    h->la = h->cap_la;
     if (closed) return INVSIM_OK;
     std::string msg = "the captured calls (" + std::to_string(h->cap_steps) + " env steps) move the handle from period " +
                       std::to_string(h->t_known ? h->t_cur : -1) + " to " + std::to_string(t_end);
-    if (la_end != h->la_valid) msg += " and change the demand lookahead state";
+    if (la_end != h->la.valid) msg += " and change the demand lookahead state";
     msg += ": a replay would not start where the graph was recorded; capture a whole number of episode cycles (" +
            std::to_string(h->horizon + (h->cm.autoreset == AR_NEXT_STEP ? 1 : 0)) +
            " steps) from a handle that has already stepped once";
@@ -1698,7 +1696,7 @@ int invsim_capture_end(invsim_handle *h, int64_t *steps) {
 int invsim_position(const invsim_handle *h, int64_t *pos) {
     if (!h || !pos) return fail(nullptr, INVSIM_EINVAL, "null argument");
     const uint64_t t = h->t_known ? (uint32_t)h->t_cur : 0xFFFFFFFFu;
-    const uint64_t la = h->la_valid ? 2u + (uint64_t)(h->la_slot & 1) : 0u;
+    const uint64_t la = h->la.valid ? 2u + (uint64_t)(h->la.slot & 1) : 0u;
     *pos = (int64_t)(t | (la << 32) | ((uint64_t)(h->demand_stream & 1) << 34));
     return INVSIM_OK;
 }

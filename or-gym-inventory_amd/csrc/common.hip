@@ -4,6 +4,7 @@
 // -> PCG64 (newsvendor.py:102, inventory_management.py:197,
 // network_management.py:303).  One thread per env, pure 32-bit integer work.
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace invsim {
 
@@ -181,8 +182,6 @@ episode_fold_groups_kernel(const double *rew, const uint8_t *term, const uint8_t
     }
     pp.flush(part + 4 * g, a, __ballot(any_done) != 0, lane);
 }
-
-static inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 hipError_t episode_fold_groups_launch(const double *rew, const uint8_t *term, const uint8_t *trunc, int32_t K,
                                       int64_t N, double *ret, double *part, hipStream_t s) {

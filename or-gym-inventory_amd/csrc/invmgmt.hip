@@ -25,6 +25,7 @@
 // A launch runs K >= 1 consecutive steps (invsim_step: K = 1; invsim_rollout:
 // K) with PCG64, I, B and the period in registers.
 #include "kernels.hpp"
+#include "launch.hpp"
 
 // invmgmt_rnd.hip compiles this file with INVSIM_IM_RND_TU: every policy kernel
 // instantiated there is the RANDOM (RandomAgent) variant (kernels.hpp ActGen),
@@ -2062,8 +2063,6 @@ __global__ void __launch_bounds__(256) im_commit_kernel(ImParams P, int slot) {
 }
 #endif  // !IM_EXT
 
-inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 #if !IM_EXT
 // the lock-step split step kernel applies (both streams)
 inline bool im_split_applies(const ImParams &p, int t_u, const PolicyIO *pol, const StepIO<int64_t, int64_t> &io) {
@@ -2075,7 +2074,7 @@ inline bool im_split_applies(const ImParams &p, int t_u, const PolicyIO *pol, co
 // is reward 0 with no flag, whose fold changes nothing (EpLane adds +0.0 to
 // returns restarted at +0.0), so the episode sink needs no work for it
 inline bool im_sink_noop(const ImParams &p, int t_u, const PolicyIO *pol, const StepIO<int64_t, int64_t> &io) {
-    return !pol && io.K == 1 && t_u >= p.periods && p.cm.autoreset == AR_NEXT_STEP;
+    return lockstep_reset_launch(pol, io, t_u, p.periods) && p.cm.autoreset == AR_NEXT_STEP;
 }
 
 // the 2-/3-role rollout kernels of the reference's default lead times apply
@@ -2093,8 +2092,7 @@ inline bool im_roll_applies(const ImParams &p, int M1, int t_u, const PolicyIO *
 template <class RG>
 hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const PolicyIO *pol,
                           const StepIO<int64_t, int64_t> &io, hipStream_t s) {
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
+    const PolicyIO &pv = pol_or_none(pol);
     using G = ImLt3<1, 5, 10>;
     using G3 = ImLt3o<1, 5, 10>;
     const dim3 g3(grid_for(p.cm.N, WAVE));
@@ -2109,7 +2107,6 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
     // equal open loop (profiles/r03/launch/g2_stage.txt)
     const bool g2 = p.cm.kn.im_roll3o_g2 < 0 ? pol != nullptr : p.cm.kn.im_roll3o_g2 == 1;
     const bool two = three && g2 && (g3.x % 2) == 0;
-    const dim3 g6(g3.x / 2);
     // INVSIM_IM_ROLL_SUB (default 65 536): the 2-role rollout as back-to-back
     // launches of at most that many envs (whole 64-env groups), each over its
     // own groups: one round of 1 024 workgroups (four per CU) per launch.
@@ -2117,26 +2114,26 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
     // 1 048 576 envs 2 433 -> 2 300 us; sub-launches of 131 072 envs (two
     // rounds each) are slower than one launch, of 16 384 far slower
     const int sub = p.cm.kn.im_roll_sub >= WAVE ? (int)std::min<int64_t>(p.cm.kn.im_roll_sub / WAVE, g3.x) : (int)g3.x;
-#define R_(B, POL)                                                                                                    \
-    do {                                                                                                              \
-        if (two) hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG, 2>), g6, dim3(6 * WAVE), 2 * G3::lds(POL), s, p, t_u, io, pv); \
-        else if (three) hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG>), g3, dim3(3 * WAVE), G3::lds(POL), s, p, t_u, io, pv); \
-        else                                                                                                          \
-            for (int g0 = 0; g0 < (int)g3.x; g0 += sub)                                                               \
-                hipLaunchKernelGGL((im_roll3_kernel<1, 5, 10, B, POL, RG>), dim3(min(sub, (int)g3.x - g0)), dim3(2 * WAVE), \
-                                   G::lds(), s, p, t_u, io, pv, g0);                                                  \
-    } while (0)
-    if (pol) {
-        if (backlog) R_(true, true);
-        else R_(false, true);
-    } else {
-#if !IM_RND && !IM_LVL
-        if (backlog) R_(true, false);
-        else R_(false, false);
+    auto launch = [&](auto B_, auto POL_) {
+        constexpr bool B = decltype(B_)::value, POL = decltype(POL_)::value;
+        if (two)
+            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG, 2>), dim3(g3.x / 2), dim3(6 * WAVE), 2 * G3::lds(POL), s, p,
+                               t_u, io, pv);
+        else if (three)
+            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG>), g3, dim3(3 * WAVE), G3::lds(POL), s, p, t_u, io, pv);
+        else
+            for (int g0 = 0; g0 < (int)g3.x; g0 += sub)
+                hipLaunchKernelGGL((im_roll3_kernel<1, 5, 10, B, POL, RG>), dim3(min(sub, (int)g3.x - g0)), dim3(2 * WAVE),
+                                   G::lds(), s, p, t_u, io, pv, g0);
+        return hipGetLastError();
+    };
+    return dispatch_bool(backlog, [&](auto B) {
+#if IM_RND || IM_LVL
+        return launch(B, std::true_type{});   // these translation units hold the policy kernels only
+#else
+        return dispatch_bool(pol != nullptr, [&](auto POL) { return launch(B, POL); });
 #endif
-    }
-#undef R_
-    return hipGetLastError();
+    });
 }
 
 // im_split_kernel's launch-time values (see the kernel's argument list): the
@@ -2172,24 +2169,58 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
     }
     return a;
 }
-// the arguments of a launch, in the kernel's order (q: its ImParams, ha: the above)
-#define IM_SPLIT_ARGS io.act, q.I, q.B, q.Rring, q.alog32, ha.acur, ha.n32, ha.hw, q, t_u, io, cur, ha.apow, ha.n, ha.nw, ha.trunc
 #endif  // !IM_EXT
 
-#define IM_DISPATCH(M1V, BL, LAUNCH)                                  \
-    switch (M1V) {                                                     \
-        case 1: if (BL) LAUNCH(1, true); else LAUNCH(1, false); break; \
-        case 2: if (BL) LAUNCH(2, true); else LAUNCH(2, false); break; \
-        case 3: if (BL) LAUNCH(3, true); else LAUNCH(3, false); break; \
-        case 4: if (BL) LAUNCH(4, true); else LAUNCH(4, false); break; \
-        case 5: if (BL) LAUNCH(5, true); else LAUNCH(5, false); break; \
-        case 6: if (BL) LAUNCH(6, true); else LAUNCH(6, false); break; \
-        case 7: if (BL) LAUNCH(7, true); else LAUNCH(7, false); break; \
-        case 8: if (BL) LAUNCH(8, true); else LAUNCH(8, false); break; \
-        default: return hipErrorInvalidValue;                          \
-    }
+// Stage count (M1 stages and the market) and backlog mode -> template arguments:
+// f(Const<M1>, std::bool_constant<backlog>)
+using ImStageCounts = Values<1, 2, 3, 4, 5, 6, 7, 8>;
+template <class F>
+hipError_t im_dispatch_shape(int M1, bool backlog, F &&f) {
+    return dispatch(ImStageCounts{}, M1, [&](auto M) {
+        return dispatch_bool(backlog, [&](auto B) { return f(M, B); });
+    }, invalid_value);
+}
+
+// The one-wave run kernel, in every translation unit: the modes this one holds
+// (the RND, LVL and EXT units: the policy instantiation, their variant of it)
+#if IM_RND || IM_LVL || IM_EXT
+using ImRunModes = Values<Run::POLICY>;
+#else
+using ImRunModes = Values<Run::STEP, Run::STEPS, Run::POLICY>;
+#endif
+inline size_t im_run_lds_bytes(const ImParams &p, int M1) {   // the obs window tile and the PTRS table
+    return (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
+}
+template <class RG>
+hipError_t im_run_kernel_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
+                                const StepIO<int64_t, int64_t> &io, hipStream_t s) {
+    const size_t lds = im_run_lds_bytes(p, M1);
+    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
+    const PolicyIO &pv = pol_or_none(pol);
+    const bool npd = p.dist >= 2 && p.dist <= 4;
+    const Run mode = run_mode(pol, io.K);
+    return im_dispatch_shape(M1, backlog, [&](auto M_, auto B_) {
+        constexpr int M = decltype(M_)::value;
+        constexpr bool B = decltype(B_)::value;
+        return dispatch_bool(t_u >= 0, [&](auto TU_) {
+            constexpr bool TU = decltype(TU_)::value;
+            return dispatch_bool(npd, [&](auto NPD_) {
+                constexpr bool NPD = decltype(NPD_)::value;
+                return dispatch(ImRunModes{}, mode, [&](auto R) {
+                    using MD = RunMode<decltype(R)::value>;
+                    hipLaunchKernelGGL((im_run_kernel<M, B, TU, MD::ONE, MD::POL, NPD, RG>), grid, block, lds, s, p, t_u, io, pv);
+                    return hipGetLastError();
+                }, invalid_value);
+            });
+        });
+    });
+}
 
 #if !IM_EXT
+// im_split_kernel's instantiations: AHEAD = the cache holds this step's demand
+// (else it is drawn inline), EARLY only for a lookahead step
+enum class ImSplit { MISS, HIT, HIT_EARLY };
+
 // The split / rollout / run dispatch of one demand stream: RG = Pcg (numpy's
 // PCG64, parity) or PhiloxGen (the fast stream; instantiated in
 // invmgmt_ph.hip).  The parity stream's lookahead cache holds generator state,
@@ -2198,107 +2229,76 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
 // other launch leaves it stale (the launch-step counter moves past it).
 template <class RG>
 hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                        const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
+                        const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s) {
     constexpr bool ph = RG::kCounter;
     sunk = im_sink_noop(p, t_u, pol, io);
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
-    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
-    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
-    const bool npd = p.dist >= 2 && p.dist <= 4;
+    // the parity stream's commit rule: before a kernel that reads cm.rng
+    auto commit = [&] {
+        const hipError_t ce = im_commit_launch(p, la.slot, s);
+        la.valid = false;
+        return ce;
+    };
     if (im_split_applies(p, t_u, pol, io)) {
-        const size_t lds2 = lds + WAVE * sizeof(int64_t);
-        const dim3 block2(2 * WAVE);
+        const size_t lds2 = im_run_lds_bytes(p, M1) + WAVE * sizeof(int64_t);
         ImParams q = p;
         if (!p.cm.kn.im_ahead) q.ahead = nullptr;
-        if constexpr (!ph) {
-            if (ahead && !q.ahead) {      // lookahead switched off: commit, then draw inline
-                const hipError_t ce = im_commit_launch(p, slot, s);
-                ahead = false;
-                if (ce != hipSuccess) return ce;
-            }
+        if (!ph && la.valid && !q.ahead) {      // lookahead switched off: commit, then draw inline
+            const hipError_t ce = commit();
+            if (ce != hipSuccess) return ce;
         }
-        const bool hit = ahead && q.ahead;
+        const bool hit = la.valid && q.ahead;
         const int gla = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;   // lookahead workgroups
-        const dim3 grid2(grid.x + gla);
-        const int cur = slot;
+        const dim3 grid2(grid_for(p.cm.N, EPW) + gla), block2(2 * WAVE);
+        const int cur = la.slot;
         // (the lookahead workgroups are the first gla of the grid: the kernel derives gla from N)
         if (p.cm.N > INT32_MAX - 2 * WAVE) return hipErrorInvalidValue;   // N travels as one dword
+        if (!ImStageCounts::has(M1)) return hipErrorInvalidValue;
         const ImSplitArgs ha = im_split_args(q, ap_host, M1, t_u, cur);
         const bool early = p.cm.N > IM_EARLY_STORES_MIN_N;   // the EARLY instantiation (lookahead steps only)
-#define S_(M, B)                                                                                        \
-    do {                                                                                                \
-        if (npd) {                                                                                      \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, RG, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, true, true, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);  \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, true, false, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);     \
-        } else {                                                                                        \
-            if (hit && early) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, RG, true>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else if (hit) hipLaunchKernelGGL((im_split_kernel<M, B, false, true, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS); \
-            else hipLaunchKernelGGL((im_split_kernel<M, B, false, false, RG>), grid2, block2, lds2, s, IM_SPLIT_ARGS);    \
-        }                                                                                               \
-    } while (0)
-        IM_DISPATCH(M1, backlog, S_)
-#undef S_
+        const ImSplit mode = !hit ? ImSplit::MISS : early ? ImSplit::HIT_EARLY : ImSplit::HIT;
+        const bool npd = p.dist >= 2 && p.dist <= 4;
         sunk = true;                  // the split kernel folds into the episode sink (if one is set)
-        ahead = q.ahead != nullptr;   // every env drew its next demand into slot cur ^ 1
-        if (ahead) slot ^= 1;
-        return hipGetLastError();
+        la.valid = q.ahead != nullptr;   // every env drew its next demand into slot cur ^ 1
+        if (la.valid) la.slot ^= 1;
+        return im_dispatch_shape(M1, backlog, [&](auto M_, auto B_) {
+            constexpr int M = decltype(M_)::value;
+            constexpr bool B = decltype(B_)::value;
+            return dispatch_bool(npd, [&](auto NPD_) {
+                constexpr bool NPD = decltype(NPD_)::value;
+                return dispatch(Values<ImSplit::MISS, ImSplit::HIT, ImSplit::HIT_EARLY>{}, mode, [&](auto S_) {
+                    constexpr bool HIT = decltype(S_)::value != ImSplit::MISS, EARLY = decltype(S_)::value == ImSplit::HIT_EARLY;
+                    // the kernel's argument list: its ImParams is q, the launch-time values ha
+                    hipLaunchKernelGGL((im_split_kernel<M, B, NPD, HIT, RG, EARLY>), grid2, block2, lds2, s, io.act, q.I, q.B,
+                                       q.Rring, q.alog32, ha.acur, ha.n32, ha.hw, q, t_u, io, cur, ha.apow, ha.n, ha.nw, ha.trunc);
+                    return hipGetLastError();
+                }, invalid_value);
+            });
+        });
     }
-    if constexpr (ph) {
-        ahead = false;
-    } else if (!(!pol && io.K == 1 && t_u >= p.periods) && ahead) {
-        // the one-wave kernel draws from the committed state (brought into
-        // cm.rng first): the cache is stale after it, unless this launch is the
-        // lock-step autoreset (no draw)
-        const hipError_t ce = im_commit_launch(p, slot, s);
-        ahead = false;
+    // every other kernel draws from the committed state (brought into cm.rng
+    // first): the cache is stale after it, unless this launch is the lock-step
+    // autoreset (no draw).  The fast stream's cache just ends.
+    if (ph) {
+        la.valid = false;
+    } else if (la.valid && !lockstep_reset_launch(pol, io, t_u, p.periods)) {
+        const hipError_t ce = commit();
         if (ce != hipSuccess) return ce;
     }
+    // the policy variants: the same rows from the translation units that hold
+    // them (RANDOM: invmgmt_rnd.hip, LEVELS: invmgmt_lvl.hip, and EXTERNAL, the
+    // caller's actions on the run kernel for any K: invmgmt_ext.hip)
+    if (pol && pol->kind == POL_RANDOM) return im_rnd_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
+    if (pol && pol->kind == POL_LEVELS) return im_lvl_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
+    if (pol && pol->kind == POL_EXTERNAL) return im_ext_launch(p, M1, backlog, t_u, *pol, io, ph, s);
     // lock-step rollout of the reference's default lead times: register windows
     // and a demand wave (im_roll3_kernel / im_roll3o_kernel), open loop or with
     // the in-kernel BaseStock / ConstantOrder agents
-#if !IM_RND
-    // RANDOM: the same rows, from the RND translation unit (invmgmt_rnd.hip)
-    if (pol && pol->kind == POL_RANDOM) return im_rnd_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
-#endif
-#if !IM_RND && !IM_LVL
-    // LEVELS: the same rows again, from the LVL translation unit (invmgmt_lvl.hip)
-    if (pol && pol->kind == POL_LEVELS) return im_lvl_launch(p, M1, backlog, t_u, *pol, io, ph, sunk, s);
-#endif
-#if !IM_RND && !IM_LVL && !IM_EXT
-    // EXTERNAL: the caller's actions, the run kernel of invmgmt_ext.hip for any K
-    if (pol && pol->kind == POL_EXTERNAL) return im_ext_launch(p, M1, backlog, t_u, *pol, io, ph, s);
-#endif
     if (im_roll_applies(p, M1, t_u, pol, io)) {
         sunk = true;                  // so do the rollout kernels
         return im_roll_launch<RG>(p, backlog, t_u, pol, io, s);
     }
-#define K_(M, B, TU, ONE, POL)                                                                          \
-    do {                                                                                                \
-        if (npd)                                                                                        \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, true, RG>), grid, block, lds, s, p, t_u, io, pv);  \
-        else                                                                                            \
-            hipLaunchKernelGGL((im_run_kernel<M, B, TU, ONE, POL, false, RG>), grid, block, lds, s, p, t_u, io, pv); \
-    } while (0)
-#define L_(M, B)                                             \
-    do {                                                     \
-        if (pol) {                                           \
-            if (t_u >= 0) K_(M, B, true, false, true);       \
-            else K_(M, B, false, false, true);               \
-        } else if (io.K == 1) {                              \
-            if (t_u >= 0) K_(M, B, true, true, false);       \
-            else K_(M, B, false, true, false);               \
-        } else {                                             \
-            if (t_u >= 0) K_(M, B, true, false, false);      \
-            else K_(M, B, false, false, false);              \
-        }                                                    \
-    } while (0)
-    IM_DISPATCH(M1, backlog, L_)
-#undef L_
-#undef K_
-    return hipGetLastError();
+    return im_run_kernel_launch<RG>(p, M1, backlog, t_u, pol, io, s);
 }
 #endif  // !IM_EXT
 
@@ -2310,32 +2310,10 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
 // K: invsim_rollout_metrics has no fused rollout).  The caller (im_launch_rg)
 // has committed the lookahead cache; the kernel does not fold into the episode
 // sink, so the host folds the output rows.
-template <class RG>
-static hipError_t im_ext_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
-                                   const StepIO<int64_t, int64_t> &io, hipStream_t s) {
-    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
-    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    const bool npd = p.dist >= 2 && p.dist <= 4;
-#define KE_(M, B, TU, NPD) hipLaunchKernelGGL((im_run_kernel<M, B, TU, false, true, NPD, RG>), grid, block, lds, s, p, t_u, io, pol)
-#define L_(M, B)                                \
-    do {                                        \
-        if (t_u >= 0) {                         \
-            if (npd) KE_(M, B, true, true);     \
-            else KE_(M, B, true, false);        \
-        } else {                                \
-            if (npd) KE_(M, B, false, true);    \
-            else KE_(M, B, false, false);       \
-        }                                       \
-    } while (0)
-    IM_DISPATCH(M1, backlog, L_)
-#undef L_
-#undef KE_
-    return hipGetLastError();
-}
 hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s) {
-    if (philox) return im_ext_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, s);
-    return im_ext_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, s);
+    if (philox) return im_run_kernel_launch<PhiloxGen>(p, M1, backlog, t_u, &pol, io, s);
+    return im_run_kernel_launch<Pcg>(p, M1, backlog, t_u, &pol, io, s);
 }
 #elif IM_RND || IM_LVL
 // invmgmt_rnd.hip / invmgmt_lvl.hip: this file compiled again, for the RANDOM /
@@ -2349,24 +2327,7 @@ static hipError_t im_var_launch_rg(const ImParams &p, int M1, bool backlog, int 
         sunk = true;
         return im_roll_launch<RG>(p, backlog, t_u, &pol, io, s);
     }
-    const size_t lds = (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
-    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    const bool npd = p.dist >= 2 && p.dist <= 4;
-#define KR_(M, B, TU, NPD) hipLaunchKernelGGL((im_run_kernel<M, B, TU, false, true, NPD, RG>), grid, block, lds, s, p, t_u, io, pol)
-#define L_(M, B)                                \
-    do {                                        \
-        if (t_u >= 0) {                         \
-            if (npd) KR_(M, B, true, true);     \
-            else KR_(M, B, true, false);        \
-        } else {                                \
-            if (npd) KR_(M, B, false, true);    \
-            else KR_(M, B, false, false);       \
-        }                                       \
-    } while (0)
-    IM_DISPATCH(M1, backlog, L_)
-#undef L_
-#undef KR_
-    return hipGetLastError();
+    return im_run_kernel_launch<RG>(p, M1, backlog, t_u, &pol, io, s);
 }
 #if IM_LVL
 hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
@@ -2382,16 +2343,16 @@ hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const
 // invmgmt_ph.hip: this file compiled a second time for the fast-stream
 // kernels (a TU of their own, so the two instantiation sets compile in parallel)
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                            const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
-    return im_launch_rg<PhiloxGen>(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);
+                            const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s) {
+    return im_launch_rg<PhiloxGen>(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);
 }
 
 INVSIM_PTRS_STATS_TU(im_ph)
 #else
 hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                         const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s) {
-    if (p.cm.philox) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);   // invmgmt_ph.hip
-    return im_launch_rg<Pcg>(p, ap_host, M1, backlog, t_u, pol, io, ahead, slot, sunk, s);
+                         const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s) {
+    if (p.cm.philox) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);   // invmgmt_ph.hip
+    return im_launch_rg<Pcg>(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);
 }
 
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s) {
@@ -2403,11 +2364,11 @@ hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s) {
 hipError_t im_reset_launch(const ImParams &p, int M1, bool backlog, const uint8_t *mask,
                            int64_t *obs, hipStream_t s) {
     if (p.cm.N == 0) return hipSuccess;
-    const dim3 grid(grid_for(p.cm.N, 256)), block(256);
-#define L_(M, B) hipLaunchKernelGGL((im_reset_kernel<M, B>), grid, block, 0, s, p, mask, obs)
-    IM_DISPATCH(M1, backlog, L_)
-#undef L_
-    return hipGetLastError();
+    return im_dispatch_shape(M1, backlog, [&](auto M, auto B) {
+        hipLaunchKernelGGL((im_reset_kernel<decltype(M)::value, decltype(B)::value>), dim3(grid_for(p.cm.N, 256)), dim3(256), 0, s,
+                           p, mask, obs);
+        return hipGetLastError();
+    });
 }
 
 INVSIM_PTRS_STATS_TU(im)

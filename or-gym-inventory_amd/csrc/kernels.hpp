@@ -319,7 +319,7 @@ struct ImParams {
     // demand lookahead cache (dist 1-4; not part of the state blob): two slots
     // of rows [state hi, state lo, next demand, 32-bit buffer] x Npad = the env's
     // PCG64 one draw past the committed state in cm.rng, and that draw.  Valid
-    // only while the host says so (invsim_handle::im_ahead, im_slot); the
+    // only while the host says so (Lookahead, below: invsim_handle::la); the
     // committed state stays exact.
     uint64_t *ahead;
 };
@@ -676,29 +676,38 @@ hipError_t episode_fold_groups_launch(const double *rew, const uint8_t *term, co
 // a reset with an episode sink set: ret[e] = 0 for the reset envs (mask, or all when null)
 hipError_t episode_ret_reset_launch(double *ret, const uint8_t *mask, int64_t N, hipStream_t s);
 
+// The demand lookahead cache of a handle (Nv/Im/NetParams::ahead), as the host
+// tracks it: `valid` = slot `slot` of the cache holds every env's next demand
+// (for the parity stream with the generator state one draw past the committed
+// state in cm.rng; the fast stream's cache holds demands only and is never
+// committed).  A run launcher takes it in and leaves it as it is after the
+// launch: a lookahead step consumes slot `slot` and fills the other one, any
+// other kernel that draws ends the cache (the parity stream's state is
+// committed to cm.rng first, *_commit_launch).
+struct Lookahead {
+    bool valid = false;
+    int slot = 0;
+};
+
 hipError_t nv_reset_launch(const NvParams &p, const uint8_t *mask, float *obs, hipStream_t s);
-// ahead / slot: the demand lookahead cache state, as for im_run_launch
 hipError_t nv_run_launch(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                         bool &ahead, int &slot, hipStream_t s);
+                         Lookahead &la, hipStream_t s);
 hipError_t nv_commit_launch(const NvParams &p, int slot, hipStream_t s);
-// the fast-stream (cm.philox) kernels, newsvendor_ph.hip (demand-only lookahead cache)
+// the fast-stream (cm.philox) kernels, newsvendor_ph.hip
 hipError_t nv_run_launch_ph(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                            bool &ahead, int &slot, hipStream_t s);
+                            Lookahead &la, hipStream_t s);
 
 hipError_t im_reset_launch(const ImParams &p, int M1, bool backlog, const uint8_t *mask,
                            int64_t *obs, hipStream_t s);
-// ahead: in = lookahead slot `slot` holds every env's next demand; out = the
-// slot (updated) does now
 // sunk: out = the launched kernel folded its rows into the episode sink
 // (Common::ep_ret), or had nothing to fold; else the caller folds the outputs
 // ap_host: the host's copy of the alpha_pow table (the split step kernel takes
 // alpha ** t by value)
 hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                         const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s);
-// the fast-stream (cm.philox) kernels, invmgmt_ph.hip; ahead / slot: the
-// fast stream's demand-only lookahead cache (never committed: it holds no state)
+                         const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s);
+// the fast-stream (cm.philox) kernels, invmgmt_ph.hip
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
-                            const StepIO<int64_t, int64_t> &io, bool &ahead, int &slot, bool &sunk, hipStream_t s);
+                            const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s);
 // the RANDOM (RND) instantiations of im_run_kernel, invmgmt_rnd.hip (both demand streams)
 // (the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
@@ -718,7 +727,7 @@ hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s);
 // (netspec.hip): which built-in topology a spec equals, and its launcher.
 enum { NET_SPEC_NONE = 0, NET_SPEC_DEFAULT = 1, NET_SPEC_CUSTOM = 2 };
 hipError_t net_spec_launch(int which, const NetParams &p, int t_u, const PolicyIO *pol,
-                           const StepIO<float, float> &io, bool &ahead, int &slot, hipStream_t s);
+                           const StepIO<float, float> &io, Lookahead &la, hipStream_t s);
 hipError_t net_commit_launch(const NetParams &p, int slot, hipStream_t s);
 hipError_t net_reset_launch(const NetParams &p, const uint8_t *mask, float *obs, hipStream_t s);
 // generic (table-walking) kernel; pol: CONSTANT / RANDOM / EXTERNAL / NET_LEVELS policy rollouts, or null

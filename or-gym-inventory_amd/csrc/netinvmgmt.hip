@@ -11,6 +11,7 @@
 //   delivery arriving this period; the same ring is the obs window),
 //   period (only when not lock-step), PCG64.
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace invsim {
 namespace {
@@ -376,8 +377,6 @@ net_reset_kernel(NetParams P, const uint8_t *__restrict__ mask, float *__restric
 
 #undef LV
 
-inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 }  // namespace
 
 size_t net_lds_bytes(const NetParams &p) {
@@ -389,65 +388,31 @@ size_t net_random_lds_bytes(const NetParams &p) { return net_lds_bytes(p) + (siz
 hipError_t net_run_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
                           hipStream_t s) {
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
-    const size_t lds = net_lds_bytes(p);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
+    if (net_lds_bytes(p) > LDS_LIMIT_BYTES) return hipErrorInvalidValue;
     if (pol && pol->kind != POL_CONSTANT && pol->kind != POL_RANDOM && pol->kind != POL_EXTERNAL &&
         pol->kind != POL_NET_LEVELS)
         return hipErrorInvalidValue;
-    if (pol && pol->kind == POL_NET_LEVELS) {
-        const size_t ldr = net_random_lds_bytes(p);          // the same action rows as RANDOM's
-        if (ldr > 160 * 1024 || !pol->levels) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses both first)
-#define KL_(TU)                                                                                        \
-    do {                                                                                               \
-        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, false, false, true>), grid, block, ldr, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, false, false, true>), grid, block, ldr, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KL_(true);
-        else KL_(false);
-#undef KL_
-        return hipGetLastError();
-    }
-    if (pol && pol->kind == POL_EXTERNAL) {
-#define KE_(TU)                                                                                        \
-    do {                                                                                               \
-        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, false, true>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KE_(true);
-        else KE_(false);
-#undef KE_
-        return hipGetLastError();
-    }
-    if (pol && pol->kind == POL_RANDOM) {
-        const size_t ldr = net_random_lds_bytes(p);
-        if (ldr > 160 * 1024) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first, INVSIM_ERANGE)
-#define KR_(TU)                                                                                        \
-    do {                                                                                               \
-        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, true, PhiloxGen, true>), grid, block, ldr, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_run_kernel<TU, true, Pcg, true>), grid, block, ldr, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KR_(true);
-        else KR_(false);
-#undef KR_
-        return hipGetLastError();
-    }
-#define K_(TU, POL)                                                                                    \
-    do {                                                                                               \
-        if (p.cm.philox) hipLaunchKernelGGL((net_run_kernel<TU, POL, PhiloxGen>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_run_kernel<TU, POL, Pcg>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-    if (t_u >= 0) {
-        if (pol) K_(true, true);
-        else K_(true, false);
-    } else {
-        if (pol) K_(false, true);
-        else K_(false, false);
-    }
-#undef K_
-    return hipGetLastError();
+    Run mode = run_mode_variant(pol, io.K, POL_NET_LEVELS);
+    if (mode == Run::STEP) mode = Run::STEPS;   // there is no single-step instantiation
+    // RANDOM and NET_LEVELS keep the step's action rows in LDS (invsim_rollout_policy
+    // refuses a topology too large for them, and NET_LEVELS without levels, first)
+    const bool rows = mode == Run::RANDOM || mode == Run::LEVELS;
+    const size_t lds = rows ? net_random_lds_bytes(p) : net_lds_bytes(p);
+    if (lds > LDS_LIMIT_BYTES || (mode == Run::LEVELS && !pol->levels)) return hipErrorInvalidValue;
+    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
+    const PolicyIO &pv = pol_or_none(pol);
+    return dispatch_bool(p.cm.philox != 0, [&](auto PH) {
+        using RG = std::conditional_t<decltype(PH)::value, PhiloxGen, Pcg>;
+        return dispatch_bool(t_u >= 0, [&](auto TU_) {
+            constexpr bool TU = decltype(TU_)::value;
+            return dispatch(Values<Run::STEPS, Run::POLICY, Run::RANDOM, Run::EXTERNAL, Run::LEVELS>{}, mode, [&](auto R) {
+                using M = RunMode<decltype(R)::value>;
+                hipLaunchKernelGGL((net_run_kernel<TU, M::POL, RG, M::RND, M::EXT, M::LVL>), grid, block, lds, s, p, t_u, io,
+                                   pv);
+                return hipGetLastError();
+            }, invalid_value);
+        });
+    });
 }
 
 hipError_t net_reset_launch(const NetParams &p, const uint8_t *mask, float *obs, hipStream_t s) {

@@ -16,6 +16,7 @@
 // Arithmetic order is the generic kernel's (and the reference's), term by term.
 #include "../../include/invsim.h"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "net_topologies.hpp"
 
 namespace invsim {
@@ -1782,138 +1783,117 @@ static size_t spec_lds_bytes() {
     return (size_t)((EPW * G::O + 3) / 4) * 4 * sizeof(float) + (size_t)G::RL * RHS_LDS_MAX * sizeof(double);
 }
 
+// The lock-step lookahead step (net_step2_kernel / net_step1_kernel) applies: one
+// open-loop step inside the episode that is not its SAME_STEP reset step.
+static bool net_step_applies(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io) {
+    return p.ahead && p.cm.kn.net_ahead && !pol && io.K == 1 && t_u >= 0 && t_u < p.T && io.obs &&
+           !(p.cm.autoreset == AR_SAME_STEP && t_u + 1 >= p.T);
+}
+// The fused rollout kernels apply: K lock-step steps that end no episode the
+// kernels cannot restart, open loop or with an in-kernel agent (ConstantOrder,
+// RANDOM, NET_LEVELS: the 3-role kernel).
+static bool net_roll_applies(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io) {
+    const bool pol_roll = pol && (pol->kind == POL_CONSTANT || pol->kind == POL_RANDOM || pol->kind == POL_NET_LEVELS) &&
+                          p.cm.kn.net_pol_roll;
+    return (!pol || pol_roll) && io.K > 1 && t_u >= 0 && !p.cm.info_rec && p.cm.kn.net_roll &&
+           (p.cm.autoreset == AR_NEXT_STEP || (p.cm.autoreset == AR_DISABLED && t_u + io.K <= p.T));
+}
+// ... of them net_roll4_kernel, for small batches, open loop: the profit on a
+// fourth wave (one workgroup per CU); net_roll3o_kernel otherwise
 template <class G>
-static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                              bool &ahead, int &slot, hipStream_t s) {
+static bool net_roll4_applies(const NetParams &p, const PolicyIO *pol) {
+    return !pol && p.cm.N <= p.cm.kn.net_roll4_max_n && !p.cm.info_demand && p.T <= NetRoll4<G>::AP;
+}
+
+template <class G, class RG>
+static hipError_t spec_launch_rg(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
+                                 Lookahead &la, hipStream_t s) {
+    constexpr bool ph = RG::kCounter;
     const size_t lds = spec_lds_bytes<G>();
-    const dim3 grid((unsigned)((p.cm.N + EPW - 1) / EPW)), block(WAVE);
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
+    const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
+    const PolicyIO &pv = pol_or_none(pol);
     // fast stream: the split step kernel with a demand-only lookahead, the
     // rollout kernels with counter-positioned draws, net_spec_kernel otherwise
-    const bool ph = p.cm.philox != 0;
-    if (p.ahead && p.cm.kn.net_ahead && !pol && io.K == 1 && t_u >= 0 && t_u < p.T && io.obs &&
-        !(p.cm.autoreset == AR_SAME_STEP && t_u + 1 >= p.T)) {
-        const bool hit = ahead;
-        const int gla = hit ? (int)((p.cm.N + WAVE - 1) / WAVE) : 0;
-        const dim3 grid2(grid.x + gla);
-        if (p.cm.kn.net_split || ph) {
-            const int gl2 = hit ? (int)((p.cm.N + 2 * WAVE - 1) / (2 * WAVE)) : 0;
-            const dim3 g2(grid.x + gl2), b2(2 * WAVE);
-            if (ph) {
-                if (hit) hipLaunchKernelGGL((net_step2_kernel<G, true, PhiloxGen>), g2, b2, lds, s, p, t_u, io, slot, gl2);
-                else hipLaunchKernelGGL((net_step2_kernel<G, false, PhiloxGen>), g2, b2, lds, s, p, t_u, io, slot, gl2);
-            } else {
-                if (hit) hipLaunchKernelGGL((net_step2_kernel<G, true>), g2, b2, lds, s, p, t_u, io, slot, gl2);
-                else hipLaunchKernelGGL((net_step2_kernel<G, false>), g2, b2, lds, s, p, t_u, io, slot, gl2);
+    if (net_step_applies(p, t_u, pol, io)) {
+        const bool hit = la.valid;
+        const int cur = la.slot;
+        la = Lookahead{true, cur ^ 1};
+        return dispatch_bool(hit, [&](auto HIT_) {
+            constexpr bool HIT = decltype(HIT_)::value;
+            if (p.cm.kn.net_split || ph) {
+                const int gl2 = hit ? (int)grid_for(p.cm.N, 2 * WAVE) : 0;
+                hipLaunchKernelGGL((net_step2_kernel<G, HIT, RG>), dim3(grid.x + gl2), dim3(2 * WAVE), lds, s, p, t_u, io, cur,
+                                   gl2);
+            } else if constexpr (!ph) {   // the one-wave step: the parity stream only
+                const int gla = hit ? (int)grid_for(p.cm.N, WAVE) : 0;
+                hipLaunchKernelGGL((net_step1_kernel<G, HIT>), dim3(grid.x + gla), block, lds, s, p, t_u, io, cur, gla);
             }
-        } else {
-            if (hit) hipLaunchKernelGGL((net_step1_kernel<G, true>), grid2, block, lds, s, p, t_u, io, slot, gla);
-            else hipLaunchKernelGGL((net_step1_kernel<G, false>), grid2, block, lds, s, p, t_u, io, slot, gla);
-        }
-        ahead = true;
-        slot ^= 1;
-        return hipGetLastError();
+            return hipGetLastError();
+        });
     }
     // the other kernels draw from cm.rng: commit the cache first (the lock-step
     // NEXT_STEP autoreset launch draws nothing and keeps it)
     if (ph) {
-        ahead = false;   // the fast stream's cache (demands only) is for a counter value now passed
-    } else if (ahead && !(!pol && io.K == 1 && t_u >= p.T)) {
-        const hipError_t ce = net_commit_launch(p, slot, s);
-        ahead = false;
+        la.valid = false;   // the fast stream's cache (demands only) is for a counter value now passed
+    } else if (la.valid && !lockstep_reset_launch(pol, io, t_u, p.T)) {
+        const hipError_t ce = net_commit_launch(p, la.slot, s);
+        la.valid = false;
         if (ce != hipSuccess) return ce;
     }
-#define K_(TU, ONE, POL)                                                                                   \
-    do {                                                                                                   \
-        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, ONE, POL, PhiloxGen>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_spec_kernel<G, TU, ONE, POL, Pcg>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-    // ... and the in-kernel ConstantOrder agent on the 3-role kernel
-    const bool rnd = pol && pol->kind == POL_RANDOM;
-    const bool lvl = pol && pol->kind == POL_NET_LEVELS;
-    if (lvl && !pol->levels) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first)
-    const bool pol_roll = pol && (pol->kind == POL_CONSTANT || rnd || lvl) && p.cm.kn.net_pol_roll;
-    if ((!pol || pol_roll) && io.K > 1 && t_u >= 0 && !p.cm.info_rec && p.cm.kn.net_roll &&
-        (p.cm.autoreset == AR_NEXT_STEP || (p.cm.autoreset == AR_DISABLED && t_u + io.K <= p.T))) {
-        const dim3 gr((unsigned)((p.cm.N + WAVE - 1) / WAVE));
-        using R3 = NetRoll3<G, NET_ROLL3_CH>;
-        // small batches, open loop: the profit on a fourth wave (one workgroup per CU)
-        if (!pol && p.cm.N <= p.cm.kn.net_roll4_max_n && !p.cm.info_demand && p.T <= NetRoll4<G>::AP) {
-            if (ph) hipLaunchKernelGGL((net_roll4_kernel<G, PhiloxGen>), gr, dim3(4 * WAVE), NetRoll4<G>::lds(), s, p, t_u, io);
-            else hipLaunchKernelGGL((net_roll4_kernel<G, Pcg>), gr, dim3(4 * WAVE), NetRoll4<G>::lds(), s, p, t_u, io);
+    const Run mode = run_mode_variant(pol, io.K, POL_NET_LEVELS);
+    if (mode == Run::LEVELS && !pol->levels) return hipErrorInvalidValue;   // (invsim_rollout_policy refuses it first)
+    if (net_roll_applies(p, t_u, pol, io)) {
+        const dim3 gr(grid_for(p.cm.N, WAVE));
+        if (net_roll4_applies<G>(p, pol)) {
+            hipLaunchKernelGGL((net_roll4_kernel<G, RG>), gr, dim3(4 * WAVE), NetRoll4<G>::lds(), s, p, t_u, io);
             return hipGetLastError();
         }
         // the 3-role net_roll3o_kernel by default (measured on MI355X, 30-step
         // launches: 32 768 envs 69 vs 97 us, 65 536 envs 140 vs 185 us against
         // net_roll_kernel)
-#define RK_(RG)                                                                                                       \
-    do {                                                                                                              \
-        if (rnd) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG, true>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
-        else if (lvl) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG, false, true>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
-        else if (pol) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, true, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
-        else if (p.cm.kn.net_roll3) hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, false, RG>), gr, dim3(3 * WAVE), R3::lds(), s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_roll_kernel<G, RG>), gr, dim3(2 * WAVE), NetRoll<G>::lds(), s, p, t_u, io);    \
-    } while (0)
-        if (ph) RK_(PhiloxGen);
-        else RK_(Pcg);
-#undef RK_
-        return hipGetLastError();
+        if (!pol && !p.cm.kn.net_roll3) {
+            hipLaunchKernelGGL((net_roll_kernel<G, RG>), gr, dim3(2 * WAVE), NetRoll<G>::lds(), s, p, t_u, io);
+            return hipGetLastError();
+        }
+        return dispatch(Values<Run::STEPS, Run::POLICY, Run::RANDOM, Run::LEVELS>{}, mode, [&](auto R) {
+            using M = RunMode<decltype(R)::value>;
+            using R3 = NetRoll3<G, NET_ROLL3_CH>;
+            hipLaunchKernelGGL((net_roll3o_kernel<G, NET_ROLL3_CH, M::POL, RG, M::RND, M::LVL>), gr, dim3(3 * WAVE), R3::lds(), s,
+                               p, t_u, io, pv);
+            return hipGetLastError();
+        }, invalid_value);
     }
-    if (pol && pol->kind == POL_RANDOM) {   // the RND variant of the policy instantiation
-#define KR_(TU)                                                                                            \
-    do {                                                                                                   \
-        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, true>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, true>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KR_(true);
-        else KR_(false);
-#undef KR_
-    } else if (pol && pol->kind == POL_EXTERNAL) {   // the EXT variant: the caller's actions, K >= 1
-#define KE_(TU)                                                                                            \
-    do {                                                                                                   \
-        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, false, true>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KE_(true);
-        else KE_(false);
-#undef KE_
-    } else if (lvl) {                               // the LVL variant: orders from the state before each step
-#define KL_(TU)                                                                                            \
-    do {                                                                                                   \
-        if (ph) hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, PhiloxGen, false, false, true>), grid, block, lds, s, p, t_u, io, pv); \
-        else hipLaunchKernelGGL((net_spec_kernel<G, TU, false, true, Pcg, false, false, true>), grid, block, lds, s, p, t_u, io, pv);         \
-    } while (0)
-        if (t_u >= 0) KL_(true);
-        else KL_(false);
-#undef KL_
-    } else if (pol) {
-        if (t_u >= 0) K_(true, false, true);
-        else K_(false, false, true);
-    } else if (io.K == 1) {
-        if (t_u >= 0) K_(true, true, false);
-        else K_(false, true, false);
-    } else {
-        if (t_u >= 0) K_(true, false, false);
-        else K_(false, false, false);
-    }
-#undef K_
-    return hipGetLastError();
+    return dispatch_bool(t_u >= 0, [&](auto TU_) {
+        constexpr bool TU = decltype(TU_)::value;
+        return dispatch(Values<Run::STEP, Run::STEPS, Run::POLICY, Run::RANDOM, Run::EXTERNAL, Run::LEVELS>{}, mode, [&](auto R) {
+            using M = RunMode<decltype(R)::value>;
+            hipLaunchKernelGGL((net_spec_kernel<G, TU, M::ONE, M::POL, RG, M::RND, M::EXT, M::LVL>), grid, block, lds, s, p, t_u,
+                               io, pv);
+            return hipGetLastError();
+        }, invalid_value);
+    });
+}
+
+template <class G>
+static hipError_t spec_launch(const NetParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
+                              Lookahead &la, hipStream_t s) {
+    if (p.cm.philox) return spec_launch_rg<G, PhiloxGen>(p, t_u, pol, io, la, s);
+    return spec_launch_rg<G, Pcg>(p, t_u, pol, io, la, s);
 }
 
 hipError_t net_commit_launch(const NetParams &p, int slot, hipStream_t s) {
     if (p.cm.N == 0 || !p.ahead) return hipSuccess;
-    hipLaunchKernelGGL(net_commit_kernel, dim3((unsigned)((p.cm.N + 255) / 256)), dim3(256), 0, s, p, slot ^ 1,
+    hipLaunchKernelGGL(net_commit_kernel, dim3(grid_for(p.cm.N, 256)), dim3(256), 0, s, p, slot ^ 1,
                        2 + p.RL);
     return hipGetLastError();
 }
 
 hipError_t net_spec_launch(int which, const NetParams &p, int t_u, const PolicyIO *pol,
-                           const StepIO<float, float> &io, bool &ahead, int &slot, hipStream_t s) {
+                           const StepIO<float, float> &io, Lookahead &la, hipStream_t s) {
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
     switch (which) {
-        case NET_SPEC_DEFAULT: return spec_launch<NetTopoDefault>(p, t_u, pol, io, ahead, slot, s);
-        case NET_SPEC_CUSTOM: return spec_launch<NetTopoCustom>(p, t_u, pol, io, ahead, slot, s);
+        case NET_SPEC_DEFAULT: return spec_launch<NetTopoDefault>(p, t_u, pol, io, la, s);
+        case NET_SPEC_CUSTOM: return spec_launch<NetTopoCustom>(p, t_u, pol, io, la, s);
         default: return hipErrorInvalidValue;
     }
 }

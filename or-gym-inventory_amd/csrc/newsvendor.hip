@@ -12,6 +12,7 @@
 // carries a kind tag {Python scalar, np.float32, np.float64} and each binary
 // op is evaluated in the dtype numpy would pick.
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace invsim {
 namespace {
@@ -1584,25 +1585,32 @@ nv_reset_kernel(NvParams P, const uint8_t *__restrict__ mask, float *__restrict_
     P.cm.period[e] = 0;
 }
 
-inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+// the lead times with a compile-time pipeline (any other: LT = -1, the ring in memory)
+using NvLeadTimes = Values<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16>;
+using NvRollLeadTimes = Values<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16>;   // the fused rollout's: a pipeline, in registers
+template <class F>
+hipError_t nv_dispatch_lt(int L, F &&f) {
+    return dispatch(NvLeadTimes{}, L, f, [&] { return f(Const<-1>{}); });
+}
 
-#define NV_LT_SWITCH(L_)              \
-    switch (p.L) {                    \
-        case 0: L_(0); break;         \
-        case 1: L_(1); break;         \
-        case 2: L_(2); break;         \
-        case 3: L_(3); break;         \
-        case 4: L_(4); break;         \
-        case 5: L_(5); break;         \
-        case 6: L_(6); break;         \
-        case 7: L_(7); break;         \
-        case 8: L_(8); break;         \
-        case 9: L_(9); break;         \
-        case 10: L_(10); break;       \
-        case 12: L_(12); break;       \
-        case 16: L_(16); break;       \
-        default: L_(-1); break;       \
-    }
+// The lock-step lookahead step (nv_step1_kernel) applies: one open-loop step
+// inside the episode that is not its SAME_STEP reset step.
+inline bool nv_step1_applies(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io) {
+    return p.ahead && p.cm.kn.nv_ahead && !pol && io.K == 1 && t_u >= 0 && t_u < p.step_limit && io.obs &&
+           !(p.cm.autoreset == AR_SAME_STEP && t_u + 1 >= p.step_limit);
+}
+// nv_step1_kernel's instantiations: HIT = the cache holds this step's demand,
+// PRODUCE = the next step is in the episode, so its demand is drawn ahead
+// (neither: nothing to gain, the run kernel takes the step)
+enum class NvStep1 { HIT_PRODUCE, HIT_LAST, MISS_PRODUCE };
+
+// The fused rollout (nv_roll_kernel) applies: K lock-step steps with a pipeline,
+// open loop or with an in-kernel agent (there is no fused EXT rollout).
+inline bool nv_roll_applies(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io) {
+    const bool ext = pol && pol->kind == POL_EXTERNAL;
+    return (!pol || (p.cm.kn.nv_pol_roll && !ext)) && io.K > 1 && t_u >= 0 && NvRollLeadTimes::has(p.L) &&
+           p.cm.autoreset != AR_SAME_STEP && p.cm.kn.nv_roll;
+}
 
 // The step / rollout dispatch of one demand stream: RG = Pcg (numpy's PCG64,
 // parity) or PhiloxGen (the fast stream; instantiated in newsvendor_ph.hip).
@@ -1610,87 +1618,61 @@ inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / b
 // and any other launch leaves it stale (the launch-step counter moves past it).
 template <class RG>
 hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                        bool &ahead, int &slot, hipStream_t s) {
+                        Lookahead &la, hipStream_t s) {
     constexpr bool ph = RG::kCounter;
     const size_t lds = (size_t)((EPW * (p.L + 5) + 3) / 4) * 4 * sizeof(float) + RHS_LDS_MAX * sizeof(double);
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
-    PolicyIO none{};
-    const PolicyIO &pv = pol ? *pol : none;
-    const bool la = p.ahead && p.cm.kn.nv_ahead;
-    if (la && !pol && io.K == 1 && t_u >= 0 && t_u < p.step_limit && io.obs &&
-        !(p.cm.autoreset == AR_SAME_STEP && t_u + 1 >= p.step_limit)) {
-        const bool produce = t_u + 1 < p.step_limit;
-        if (ahead || produce) {
-            const bool hit = ahead;
-            // lookahead workgroups: two per 64 envs (one per sampler branch) to
-            // draw, one to commit the parity stream's state when the chain ends
-            const int gla = hit ? (produce ? 2 : (ph ? 0 : 1)) * (int)grid_for(p.cm.N, WAVE) : 0;
-            const dim3 grid2(grid.x + gla);
-            const int cur = slot;
-#define S_(X)                                                                                                \
-    do {                                                                                                     \
-        if (hit && produce) hipLaunchKernelGGL((nv_step1_kernel<X, true, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);      \
-        else if (hit) hipLaunchKernelGGL((nv_step1_kernel<X, true, false, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);           \
-        else hipLaunchKernelGGL((nv_step1_kernel<X, false, true, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);                    \
-    } while (0)
-            NV_LT_SWITCH(S_)
-#undef S_
-            if (produce) {
-                ahead = true;
-                slot ^= 1;
-            } else {
-                ahead = false;   // cm.rng committed by the lookahead workgroups
-            }
-            return hipGetLastError();
-        }
+    const PolicyIO &pv = pol_or_none(pol);
+    const bool produce = t_u + 1 < p.step_limit;
+    if (nv_step1_applies(p, t_u, pol, io) && (la.valid || produce)) {
+        const bool hit = la.valid;
+        // lookahead workgroups: two per 64 envs (one per sampler branch) to
+        // draw, one to commit the parity stream's state when the chain ends
+        const int gla = hit ? (produce ? 2 : (ph ? 0 : 1)) * (int)grid_for(p.cm.N, WAVE) : 0;
+        const dim3 grid2(grid.x + gla);
+        const int cur = la.slot;
+        const NvStep1 step = !hit ? NvStep1::MISS_PRODUCE : produce ? NvStep1::HIT_PRODUCE : NvStep1::HIT_LAST;
+        if (produce) la = Lookahead{true, la.slot ^ 1};
+        else la.valid = false;   // cm.rng committed by the lookahead workgroups
+        return nv_dispatch_lt(p.L, [&](auto X) {
+            constexpr int LT = decltype(X)::value;
+            return dispatch(Values<NvStep1::HIT_PRODUCE, NvStep1::HIT_LAST, NvStep1::MISS_PRODUCE>{}, step, [&](auto S) {
+                constexpr NvStep1 ST = decltype(S)::value;
+                constexpr bool HIT = ST != NvStep1::MISS_PRODUCE, PRODUCE = ST != NvStep1::HIT_LAST;
+                hipLaunchKernelGGL((nv_step1_kernel<LT, HIT, PRODUCE, RG>), grid2, block, lds, s, p, t_u, io, cur, gla);
+                return hipGetLastError();
+            }, invalid_value);
+        });
     }
-    if (ahead) {   // the one-wave kernel reads cm.rng: commit, the cache ends
-        const hipError_t ce = ph ? hipSuccess : nv_commit_launch(p, slot, s);
-        ahead = false;
+    if (la.valid) {   // every other kernel reads cm.rng: commit (the parity stream), the cache ends
+        const hipError_t ce = ph ? hipSuccess : nv_commit_launch(p, la.slot, s);
+        la.valid = false;
         if (ce != hipSuccess) return ce;
     }
-    const bool rnd = pol && pol->kind == POL_RANDOM;
-    const bool ext = pol && pol->kind == POL_EXTERNAL;   // the run kernel only: there is no fused EXT rollout
-    if ((!pol || (p.cm.kn.nv_pol_roll && !ext)) && io.K > 1 && t_u >= 0 && p.L > 0 &&
-        p.cm.autoreset != AR_SAME_STEP && p.cm.kn.nv_roll) {
+    const Run mode = run_mode_variant(pol, io.K, POL_NONE);
+    if (nv_roll_applies(p, t_u, pol, io)) {
         const dim3 gr(grid_for(p.cm.N, WAVE)), br(NV_ROLL_WAVES * WAVE);
-        bool done = true;
-#define R_(X)                                                                                              \
-    do {                                                                                                   \
-        if (X > 0) {                                                                                       \
-            if (rnd) hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), true, RG, true>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
-            else if (pol) hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), true, RG>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
-            else hipLaunchKernelGGL((nv_roll_kernel<(X > 0 ? X : 1), false, RG>), gr, br, NvRoll<(X > 0 ? X : 1)>::lds(), s, p, t_u, io, pv); \
-        } else done = false;                                                                               \
-    } while (0)
-        NV_LT_SWITCH(R_)
-#undef R_
-        if (done) return hipGetLastError();
+        return dispatch(NvRollLeadTimes{}, p.L, [&](auto X) {
+            constexpr int LT = decltype(X)::value;
+            return dispatch(Values<Run::STEPS, Run::POLICY, Run::RANDOM>{}, mode, [&](auto R) {
+                using M = RunMode<decltype(R)::value>;
+                hipLaunchKernelGGL((nv_roll_kernel<LT, M::POL, RG, M::RND>), gr, br, NvRoll<LT>::lds(), s, p, t_u, io, pv);
+                return hipGetLastError();
+            }, invalid_value);
+        }, invalid_value);
     }
-#define K_(X, TU, ONE, POL) hipLaunchKernelGGL((nv_run_kernel<X, TU, ONE, POL, RG>), grid, block, lds, s, p, t_u, io, pv)
-#define L_(X)                                          \
-    do {                                               \
-        if (rnd) {                                     \
-            if (t_u >= 0) hipLaunchKernelGGL((nv_run_kernel<X, true, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);   \
-            else hipLaunchKernelGGL((nv_run_kernel<X, false, false, true, RG, true>), grid, block, lds, s, p, t_u, io, pv);            \
-        } else if (ext) {                              \
-            if (t_u >= 0) hipLaunchKernelGGL((nv_run_kernel<X, true, false, true, RG, false, true>), grid, block, lds, s, p, t_u, io, pv);  \
-            else hipLaunchKernelGGL((nv_run_kernel<X, false, false, true, RG, false, true>), grid, block, lds, s, p, t_u, io, pv);           \
-        } else if (pol) {                              \
-            if (t_u >= 0) K_(X, true, false, true);    \
-            else K_(X, false, false, true);            \
-        } else if (io.K == 1) {                        \
-            if (t_u >= 0) K_(X, true, true, false);    \
-            else K_(X, false, true, false);            \
-        } else {                                       \
-            if (t_u >= 0) K_(X, true, false, false);   \
-            else K_(X, false, false, false);           \
-        }                                              \
-    } while (0)
-    NV_LT_SWITCH(L_)
-#undef L_
-#undef K_
-    return hipGetLastError();
+    return nv_dispatch_lt(p.L, [&](auto X) {
+        constexpr int LT = decltype(X)::value;
+        return dispatch_bool(t_u >= 0, [&](auto TU_) {
+            constexpr bool TU = decltype(TU_)::value;
+            return dispatch(Values<Run::STEP, Run::STEPS, Run::POLICY, Run::RANDOM, Run::EXTERNAL>{}, mode, [&](auto R) {
+                using M = RunMode<decltype(R)::value>;
+                hipLaunchKernelGGL((nv_run_kernel<LT, TU, M::ONE, M::POL, RG, M::RND, M::EXT>), grid, block, lds, s, p,
+                                   t_u, io, pv);
+                return hipGetLastError();
+            }, invalid_value);
+        });
+    });
 }
 
 }  // namespace
@@ -1699,9 +1681,9 @@ hipError_t nv_launch_rg(const NvParams &p, int t_u, const PolicyIO *pol, const S
 // newsvendor_ph.hip: this file compiled a second time for the fast-stream
 // kernels (a TU of their own, so the two instantiation sets compile in parallel)
 hipError_t nv_run_launch_ph(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                            bool &ahead, int &slot, hipStream_t s) {
+                            Lookahead &la, hipStream_t s) {
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
-    return nv_launch_rg<PhiloxGen>(p, t_u, pol, io, ahead, slot, s);
+    return nv_launch_rg<PhiloxGen>(p, t_u, pol, io, la, s);
 }
 
 INVSIM_PTRS_STATS_TU(nv_ph)
@@ -1713,10 +1695,10 @@ hipError_t nv_commit_launch(const NvParams &p, int slot, hipStream_t s) {
 }
 
 hipError_t nv_run_launch(const NvParams &p, int t_u, const PolicyIO *pol, const StepIO<float, float> &io,
-                         bool &ahead, int &slot, hipStream_t s) {
+                         Lookahead &la, hipStream_t s) {
     if (p.cm.N == 0 || io.K <= 0) return hipSuccess;
-    if (p.cm.philox) return nv_run_launch_ph(p, t_u, pol, io, ahead, slot, s);   // newsvendor_ph.hip
-    return nv_launch_rg<Pcg>(p, t_u, pol, io, ahead, slot, s);
+    if (p.cm.philox) return nv_run_launch_ph(p, t_u, pol, io, la, s);   // newsvendor_ph.hip
+    return nv_launch_rg<Pcg>(p, t_u, pol, io, la, s);
 }
 
 hipError_t nv_reset_launch(const NvParams &p, const uint8_t *mask, float *obs, hipStream_t s) {
