@@ -385,6 +385,61 @@ int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const v
                        void *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
                        void *actions, double *metrics, void *stream);
 
+/* ---- Gaussian MLP actor: rollout collection for on-policy learners (the
+ * reference's benchmark_*_sb3_rllib.py train SB3 PPO / A2C and RLlib PPO, whose
+ * rollouts come from a diagonal Gaussian around the network's output).  The
+ * sampling launch is the MLP actor's kernel with one more stage: after the last
+ * layer every env draws action_dim standard normals from its action generator
+ * (the RandomAgent section's PCG64 streams: seeding, checkpointing and sharding
+ * are theirs), and the launch reports the sample, its log-probability and the
+ * converted action.  The critic is not part of this: values do not feed back
+ * into the closed loop, a caller evaluates them over the returned obs rows.
+ *
+ * Contract (on top of "MLP actor"; A = action_dim):
+ *   draws      every launch step of every env < N consumes exactly A standard
+ *              normals z from the env's action generator, in ascending action
+ *              index, whether or not the step is applied (a NEXT_STEP reset step
+ *              draws too, as RANDOM does).  z is numpy 2.2.6's
+ *              Generator.standard_normal (random_standard_normal: the 256-level
+ *              ziggurat over ki / wi / fi, unfused f64 arithmetic), bit for bit
+ *              up to the device library's log1p / exp on the 1.4 % of draws
+ *              that leave the fast path.  The demand `rng` rows and philox_step
+ *              are never touched.
+ *   sample     zf = (float)z;  raw[a] = fmaf(std[a], zf, mean[a]), where mean is
+ *              what invsim_mlp_actions reports as raw.
+ *   log-prob   acc = (float)(-0.91893853320467274178 * (double)A), computed on
+ *              the host; for a ascending: acc = fmaf(-0.5f * zf, zf, acc), then
+ *              acc = acc - log_std[a].  The density of the unclipped sample,
+ *              which is what SB3 stores.
+ *   conversion exactly the MLP actor's, applied to raw.
+ *
+ * invsim_mlp_set_gaussian copies std and log_std (host [A] arrays) into the
+ * object's parameter blob; it waits for the device first and is refused during
+ * capture.  std must be finite and >= 0 and log_std finite (INVSIM_EINVAL).
+ * The library calls no transcendental: the caller supplies both arrays and
+ * answers for their agreement.  NULL std clears the Gaussian.
+ *
+ * invsim_mlp_sample is one launch.  Each output may be NULL, but not all of
+ * them; whatever is requested, the generators advance by A normals.  Without a
+ * Gaussian on m or without action generators on h (invsim_set_action_rng) it
+ * returns INVSIM_EINVAL.  It does not touch env state and is legal inside a
+ * capture bracket: the generators are device-resident, so a replay continues
+ * the stream.
+ *
+ * invsim_rollout_mlp_sample is invsim_rollout_mlp with the sampling launch in
+ * place of the deterministic one; raw [K][N][A] and logp [K][N] may be NULL.
+ * Everything else is unchanged: every refusal comes before the first launch,
+ * SAME_STEP refused, the sink folded once, capture, both demand streams, every
+ * graph, per-env periods. */
+int invsim_mlp_set_gaussian(invsim_handle *h, invsim_mlp *m, const float *std /* host [A], NULL clears */,
+                            const float *log_std /* host [A] */);
+int invsim_mlp_sample(invsim_handle *h, const invsim_mlp *m, const void *obs /* [N][O], obs dtype */,
+                      void *actions /* [N][A], action dtype */, float *raw /* [N][A] */, float *mean /* [N][A] */,
+                      float *logp /* [N] */, void *stream);
+int invsim_rollout_mlp_sample(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0 /* [N][O] */,
+                              void *obs, double *reward, uint8_t *terminated, uint8_t *truncated, void *actions,
+                              float *raw /* [K][N][A] */, float *logp /* [K][N] */, double *metrics, void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

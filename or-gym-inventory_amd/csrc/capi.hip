@@ -99,6 +99,10 @@ struct invsim_mlp {
     float *blob = nullptr;
     void *obs_row = nullptr;    // [N][O], obs dtype
     void *act_row = nullptr;    // [N][A], action dtype
+    // the Gaussian around the output (invsim_mlp_set_gaussian): two [A] rows of the blob
+    float *g_std = nullptr, *g_log_std = nullptr;
+    bool gauss = false;
+    float logp0 = 0.0f;         // (float)(-0.5 * log(2 pi) * A)
 };
 
 namespace {
@@ -1333,6 +1337,8 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
         }
     }
     const size_t o_dev = reserve((sizeof(MlpDev) + 3) / 4);
+    const size_t o_gs = reserve(A), o_gl = reserve(A);     // invsim_mlp_set_gaussian's std and log_std
+    m->logp0 = (float)(-0.91893853320467274178 * (double)A);
     DeviceGuard g(h->device);
     const size_t esz = i64 ? 8 : 4;
     const size_t n_el = (size_t)std::max<int64_t>(h->N, 1);
@@ -1354,6 +1360,7 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
         }
         std::memcpy(&blob[o_dev], &d, sizeof(MlpDev));
         m->dev_copy = (const MlpDev *)(base + o_dev);
+        m->g_std = m->blob + o_gs, m->g_log_std = m->blob + o_gl;
         e = hipMemcpy(m->blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
@@ -1386,9 +1393,67 @@ int invsim_mlp_actions(invsim_handle *h, const invsim_mlp *m, const void *obs, v
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp launch");
 }
 
-int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0, void *obs, double *reward,
-                       uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream) {
-    TraceRange tr_("invsim_rollout_mlp");
+// what the sampling launch needs beyond the network: a Gaussian on m and the
+// action generators on h; fills the launch's arguments but mean and logp
+static int mlp_sample_args(invsim_handle *h, const invsim_mlp *m, MlpSample &sm) {
+    if (!m->gauss)
+        return fail(h, INVSIM_EINVAL, "no Gaussian set on this invsim_mlp: give std and log_std with "
+                                      "invsim_mlp_set_gaussian");
+    if (!h->arng)
+        return fail(h, INVSIM_EINVAL, "no action generators attached: seed a buffer with invsim_seed_action_rng and "
+                                      "attach it with invsim_set_action_rng");
+    sm = MlpSample{nullptr, nullptr, h->arng, h->Npad, m->g_std, m->g_log_std, m->logp0};
+    return INVSIM_OK;
+}
+
+int invsim_mlp_set_gaussian(invsim_handle *h, invsim_mlp *m, const float *std, const float *log_std) {
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (int rc = refuse_in_capture(h, "mlp_set_gaussian")) return rc;
+    if (!std) {
+        m->gauss = false;
+        return INVSIM_OK;
+    }
+    if (!log_std) return fail(h, INVSIM_EINVAL, "std without log_std");
+    const int A = h->act_dim;
+    for (int a = 0; a < A; a++) {
+        if (!std::isfinite(std[a]) || !(std[a] >= 0.0f)) return fail(h, INVSIM_EINVAL, "std must be finite and >= 0");
+        if (!std::isfinite(log_std[a])) return fail(h, INVSIM_EINVAL, "log_std must be finite");
+    }
+    // the blob's rows are overwritten: wait for every launch that may still read them
+    DeviceGuard g(h->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(m->g_std, std, A * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->g_log_std, log_std, A * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        m->gauss = false;
+        return hip_fail(h, e, "mlp_set_gaussian");
+    }
+    m->gauss = true;
+    return INVSIM_OK;
+}
+
+int invsim_mlp_sample(invsim_handle *h, const invsim_mlp *m, const void *obs, void *actions, float *raw, float *mean,
+                      float *logp, void *stream) {
+    TraceRange tr_("invsim_mlp_sample");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (h->N && !obs) return fail(h, INVSIM_EINVAL, "null obs");
+    if (!actions && !raw && !mean && !logp) return fail(h, INVSIM_EINVAL, "no output: every output pointer is null");
+    MlpSample sm{};
+    if (int rc = mlp_sample_args(h, m, sm)) return rc;
+    sm.mean = mean, sm.logp = logp;
+    DeviceGuard g(h->device);
+    hipError_t e = mlp_sample_launch(m->dev, m->dev_copy, h->family == INVSIM_INVMGMT, obs, actions, raw, sm, h->N,
+                                     (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp sample launch");
+}
+
+// invsim_rollout_mlp, and with `sample` invsim_rollout_mlp_sample: the same loop
+// with the sampling launch (raw [K][N][A], logp [K][N], either may be null)
+static int rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0, void *obs, double *reward,
+                       uint8_t *terminated, uint8_t *truncated, void *actions, float *raw, float *logp, double *metrics,
+                       void *stream, bool sample) {
     if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
     if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
     if (K == 0) return INVSIM_OK;
@@ -1396,6 +1461,9 @@ int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const v
     if (h->N && !obs0) return fail(h, INVSIM_EINVAL, "null obs0: the network's first input is the observation the env "
                                                      "last returned");
     if (int rc = metric_rollout_checks(h, reward, terminated, truncated)) return rc;
+    MlpSample sm{};
+    if (sample)
+        if (int rc = mlp_sample_args(h, m, sm)) return rc;
     const PolicyIO p = external_policy(h, metrics);
     const bool i64 = h->family == INVSIM_INVMGMT;
     const size_t o_row = (size_t)h->N * h->obs_dim * (i64 ? 8 : 4), a_row = (size_t)h->N * h->act_dim * (i64 ? 8 : 4);
@@ -1420,9 +1488,15 @@ int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const v
     for (int k = 0; k < K; k++) {
         void *a_k = actions ? (char *)actions + k * a_row : m->act_row;
         void *o_k = obs ? (char *)obs + k * o_row : m->obs_row;   // in == o_k then: read before it is overwritten (stream order)
-        hipError_t e = mlp_launch(m->dev, m->dev_copy, i64, in, a_k, nullptr, h->N, s);
-        if (e != hipSuccess) return hip_fail(h, e, "mlp launch");
         const size_t r = (size_t)k * h->N;
+        hipError_t e;
+        if (sample) {
+            sm.logp = logp ? logp + r : nullptr;
+            e = mlp_sample_launch(m->dev, m->dev_copy, i64, in, a_k, raw ? raw + r * h->act_dim : nullptr, sm, h->N, s);
+        } else {
+            e = mlp_launch(m->dev, m->dev_copy, i64, in, a_k, nullptr, h->N, s);
+        }
+        if (e != hipSuccess) return hip_fail(h, e, "mlp launch");
         if (int rc = steps_launch(h, 1, a_k, o_k, reward ? reward + r : nullptr, terminated ? terminated + r : nullptr,
                                   truncated ? truncated + r : nullptr, nullptr, s, &p))
             return rc;
@@ -1433,6 +1507,19 @@ int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const v
         if (e != hipSuccess) return hip_fail(h, e, "episode sink fold");
     }
     return steps_end(h, s);
+}
+
+int invsim_rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0, void *obs, double *reward,
+                       uint8_t *terminated, uint8_t *truncated, void *actions, double *metrics, void *stream) {
+    TraceRange tr_("invsim_rollout_mlp");
+    return rollout_mlp(h, K, m, obs0, obs, reward, terminated, truncated, actions, nullptr, nullptr, metrics, stream, false);
+}
+
+int invsim_rollout_mlp_sample(invsim_handle *h, int32_t K, const invsim_mlp *m, const void *obs0, void *obs,
+                              double *reward, uint8_t *terminated, uint8_t *truncated, void *actions, float *raw,
+                              float *logp, double *metrics, void *stream) {
+    TraceRange tr_("invsim_rollout_mlp_sample");
+    return rollout_mlp(h, K, m, obs0, obs, reward, terminated, truncated, actions, raw, logp, metrics, stream, true);
 }
 
 int invsim_action_rng_bytes(const invsim_handle *h, int64_t *bytes) {

@@ -20,7 +20,9 @@
 #include <type_traits>
 
 #include "../../include/invsim.h"
+#include "device_common.hpp"
 #include "mlp_policy.hpp"
+#include "numpy_normal.hpp"
 
 namespace invsim {
 namespace {
@@ -92,9 +94,20 @@ __device__ __forceinline__ long long mlp_convert(float r, double lo, double hi, 
     return (long long)x;     // toward zero
 }
 
-template <bool I64>
+template <class T, class... R>
+__device__ __forceinline__ const T &mlp_first(const T &t, const R &...) {
+    return t;
+}
+
+// SAMPLE (include/invsim.h "Gaussian MLP actor"): a compile-time variant that
+// draws the action noise after the last layer.  Its MlpSample is the pack Sm,
+// which is empty otherwise: the deterministic instantiations keep the
+// arguments, and so the code, they had.
+template <bool I64, bool SAMPLE = false, class... Sm>
 __global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restrict__ mp, const void *__restrict__ obs_,
-                                                         void *__restrict__ act_, float *__restrict__ raw, int64_t N) {
+                                                         void *__restrict__ act_, float *__restrict__ raw, int64_t N,
+                                                         Sm... sm_) {
+    static_assert(sizeof...(Sm) == (SAMPLE ? 1 : 0), "SAMPLE takes one MlpSample");
     mlp_cdev m = *mlp_const(mp);
     using Obs = typename std::conditional<I64, long long, float>::type;
     extern __shared__ float mlp_lds[];
@@ -132,14 +145,47 @@ __global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restric
         __syncthreads();
     }
 
-    // output: [N][A] rows of this workgroup's envs, contiguous again
     const int A = m.dims[m.n_layers];
     const float *res = mlp_lds + (m.n_layers & 1) * half;
+
+    // sampling: wave 0, lane = env.  The env's generator draws A normals in
+    // ascending action index; the sample goes to the other buffer (the last
+    // layer's input, free since the barrier above, rows >= A), the epilogue
+    // below spreads it.  Lanes at or past N draw nothing and store nothing.
+    if constexpr (SAMPLE) {
+        const MlpSample &sm = mlp_first(sm_...);
+        if (wave == 0) {
+            const int64_t e = env0 + lane;
+            if (e < N) {
+                const RngSoA rows = act_rng_rows(sm.arng, sm.npad);
+                Pcg g = rows.load(e);
+                float *smp = mlp_lds + ((m.n_layers + 1) & 1) * half + lane;
+                mlp_cfloat sd = mlp_const(sm.std), lsd = mlp_const(sm.log_std);
+                float acc = sm.logp0;
+                for (int a = 0; a < A; a++) {
+                    const float zf = (float)np_standard_normal(g);
+                    smp[a * MLP_ROW] = __builtin_fmaf(sd[a], zf, res[a * MLP_ROW + lane]);
+                    acc = __builtin_fmaf(-0.5f * zf, zf, acc);
+                    acc = acc - lsd[a];
+                }
+                if (sm.logp) sm.logp[e] = acc;
+                rows.store_state(e, g);
+            }
+        }
+        __syncthreads();
+    }
+
+    // output: [N][A] rows of this workgroup's envs, contiguous again
     const int64_t left = (N - env0) * A;
     for (int e = tid; e < MLP_ENVS * A && e < left; e += threads) {
         const int env = e / A, a = e - env * A;
-        const float r = res[a * MLP_ROW + env];
+        float r = res[a * MLP_ROW + env];
         const int64_t g = env0 * A + e;
+        if constexpr (SAMPLE) {
+            const MlpSample &sm = mlp_first(sm_...);
+            if (sm.mean) sm.mean[g] = r;
+            r = mlp_lds[((m.n_layers + 1) & 1) * half + a * MLP_ROW + env];
+        }
         if (raw) raw[g] = r;
         if (act_) {
             if (I64) ((long long *)act_)[g] = mlp_convert(r, m.clip ? m.lo_d[a] : 0.0, m.clip ? m.hi_d[a] : 0.0, m.clip != 0);
@@ -153,11 +199,14 @@ constexpr int MLP_LDS_MAX = 2 * MLP_WIDTH * MLP_ROW * (int)sizeof(float);   // 1
 }  // namespace
 
 hipError_t mlp_prepare() {
-    hipError_t e = hipFuncSetAttribute((const void *)mlp_policy_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       MLP_LDS_MAX);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void *)mlp_policy_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               MLP_LDS_MAX);
+    const void *kernels[] = {(const void *)mlp_policy_kernel<true>, (const void *)mlp_policy_kernel<false>,
+                             (const void *)mlp_policy_kernel<true, true, MlpSample>,
+                             (const void *)mlp_policy_kernel<false, true, MlpSample>};
+    for (const void *k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_MAX);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t mlp_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw, int64_t N,
@@ -168,6 +217,17 @@ hipError_t mlp_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *
     const dim3 grid((unsigned)((N + MLP_ENVS - 1) / MLP_ENVS)), block(mlp_threads(m));
     if (i64) hipLaunchKernelGGL(mlp_policy_kernel<true>, grid, block, lds, s, dev, obs, actions, raw, N);
     else hipLaunchKernelGGL(mlp_policy_kernel<false>, grid, block, lds, s, dev, obs, actions, raw, N);
+    return hipGetLastError();
+}
+
+hipError_t mlp_sample_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw,
+                             const MlpSample &sm, int64_t N, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    const size_t lds = mlp_lds_bytes(m);
+    if (lds > (size_t)MLP_LDS_MAX) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((N + MLP_ENVS - 1) / MLP_ENVS)), block(mlp_threads(m));
+    if (i64) hipLaunchKernelGGL((mlp_policy_kernel<true, true, MlpSample>), grid, block, lds, s, dev, obs, actions, raw, N, sm);
+    else hipLaunchKernelGGL((mlp_policy_kernel<false, true, MlpSample>), grid, block, lds, s, dev, obs, actions, raw, N, sm);
     return hipGetLastError();
 }
 

@@ -48,4 +48,20 @@ hipError_t mlp_prepare();
 hipError_t mlp_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw, int64_t N,
                       hipStream_t s);
 
+// The sampling launch's further arguments (include/invsim.h "Gaussian MLP
+// actor"): a by-value kernel argument of the sampling instantiations only.
+struct MlpSample {
+    float *mean;                    // [N][A]: the network's output (mlp_launch's raw), may be null
+    float *logp;                    // [N], may be null
+    uint64_t *arng;                 // the action generators [4][Npad] (act_rng_rows)
+    int64_t npad;
+    const float *std, *log_std;     // [A], in the parameter blob
+    float logp0;                    // (float)(-0.5 * log(2 pi) * A)
+};
+
+// one launch: as mlp_launch with raw = the sample fmaf(std, z, mean) and actions
+// = its conversion; every env < N draws A normals whatever outputs are null
+hipError_t mlp_sample_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw,
+                             const MlpSample &sm, int64_t N, hipStream_t s);
+
 }  // namespace invsim

@@ -29,6 +29,8 @@ _LAZY = {
     "RandomAgent": "policies",
     "TorchPolicyAgent": "policies",
     "MLPPolicyAgent": "policies",
+    "GaussianMLPPolicyAgent": "policies",
+    "collect_rollout": "policies",
     "LevelsAgent": "policies",
     "NetLevelsAgent": "policies",
     "evaluate_levels": "policies",

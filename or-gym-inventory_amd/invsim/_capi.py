@@ -32,6 +32,7 @@ EXPORTS = (
     "invsim_action_rng_bytes", "invsim_seed_action_rng", "invsim_set_action_rng", "invsim_sample_actions",
     "invsim_rollout_metrics",
     "invsim_mlp_create", "invsim_mlp_destroy", "invsim_mlp_actions", "invsim_rollout_mlp",
+    "invsim_mlp_set_gaussian", "invsim_mlp_sample", "invsim_rollout_mlp_sample",
     "invsim_set_policy_levels", "invsim_set_policy_net_levels",
 )
 ABI_VERSION = 4
@@ -140,6 +141,9 @@ def _declare(lib):
         "invsim_mlp_destroy": ([P], None),
         "invsim_mlp_actions": ([H, P, P, P, P, P], C.c_int),
         "invsim_rollout_mlp": ([H, I32, P, P, P, P, P, P, P, P, P], C.c_int),
+        "invsim_mlp_set_gaussian": ([H, P, P, P], C.c_int),
+        "invsim_mlp_sample": ([H, P, P, P, P, P, P, P], C.c_int),
+        "invsim_rollout_mlp_sample": ([H, I32, P, P, P, P, P, P, P, P, P, P, P], C.c_int),
         "invsim_set_policy_levels": ([H, P, P], C.c_int),
         "invsim_set_policy_net_levels": ([H, P, P], C.c_int),
     }

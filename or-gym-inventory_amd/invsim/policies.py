@@ -46,7 +46,11 @@ wrapper's post-processing of the network's output.  A plain feed-forward actor
 (Linear / ReLU / Tanh, at most 5 layers of at most 256 units) can instead be
 handed to the library as an ``MLPPolicyAgent``: the network is then a HIP
 kernel of its own and the closed loop is issued in C (``invsim_rollout_mlp``),
-two launches per step with no Python between them.
+two launches per step with no Python between them.  A
+``GaussianMLPPolicyAgent`` is that actor with a diagonal Gaussian around it,
+sampled in the same kernel: ``collect_rollout`` returns what an on-policy
+learner (the scripts' SB3 ``PPO`` / ``A2C``) stores per step, log-probabilities
+included.
 
 ``evaluate_agent(agent, env_cls, env_config, n_episodes, seed_offset)`` returns
 the reference's summary columns (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -600,6 +604,117 @@ class MLPPolicyAgent(_Agent):
         return obj
 
 
+class GaussianMLPPolicyAgent(MLPPolicyAgent):
+    """An ``MLPPolicyAgent`` that samples: a diagonal Gaussian around the
+    network's output, the stochastic actor an on-policy learner (SB3 ``PPO`` /
+    ``A2C``) collects its rollouts from.  The network kernel draws the noise
+    itself, ``action_dim`` of numpy's ``standard_normal`` per env and step from
+    the env's action generator, and reports the sample, its log-probability and
+    the converted action (``include/invsim.h``, "Gaussian MLP actor"):
+    ``raw = fmaf(std, (float)z, mean)``, ``log_prob`` the density of the
+    unclipped sample, as SB3 stores it.
+
+    ``log_std`` ``[action_dim]`` is SB3's state-independent parameter;
+    ``std = exp(log_std)`` is computed here in float64 and rounded to float32.
+    ``seed`` and the action stream follow ``RandomAgent``'s rule: env with
+    global index g draws from ``Generator(PCG64(SeedSequence(2**64 + seed +
+    g)))``; the first meeting with an env seeds its action generators, and the
+    agent re-attaches its own buffer if another has been attached since.  The
+    other arguments are ``MLPPolicyAgent``'s.
+
+    ``collect_rollout(env, agent, K, obs0)`` is the rollout buffer's content
+    in one C call; ``env.mlp_sample(agent, obs)`` the single launch;
+    ``rollout_policy`` / ``evaluate_agent`` take the agent with their usual
+    keys (``actions`` then holds the sampled, converted actions)."""
+
+    def __init__(self, layers, log_std, seed=None, name="GaussianMLP", **kw):
+        super().__init__(layers, name=name, **kw)
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        _require_agreed_seed(seed, world)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little") >> 1      # 63 bits of OS entropy
+        self.seed = int(seed)
+        self.log_std = _f32(log_std, (self.dims[-1],), "log_std")
+        if not np.all(np.isfinite(self.log_std)):
+            raise ValueError("log_std must be finite")
+        with np.errstate(over="ignore"):
+            self.std = np.exp(self.log_std.astype(np.float64)).astype(np.float32)
+        if not np.all(np.isfinite(self.std)):
+            raise ValueError("exp(log_std) must be finite in float32")
+        self._bufs = weakref.WeakKeyDictionary()       # env -> the generators this agent seeded for it
+
+    @classmethod
+    def from_module(cls, module, log_std=None, **kw):
+        """``MLPPolicyAgent.from_module`` plus ``log_std`` (SB3's ``policy.log_std``)."""
+        if log_std is None:
+            raise TypeError("GaussianMLPPolicyAgent.from_module needs log_std")
+        return super().from_module(module, log_std=log_std, **kw)
+
+    def device_object(self, env):
+        """The ``invsim_mlp`` of this network on ``env`` with its Gaussian set, and
+        this agent's action generators attached to ``env``."""
+        fresh = self._objs.get(env) is None or self._objs[env][0] is not env._h
+        obj = super().device_object(env)
+        if fresh:
+            _capi.check(env._lib.invsim_mlp_set_gaussian(env._h, obj, self.std.ctypes.data, self.log_std.ctypes.data),
+                        env._h, "mlp_set_gaussian")
+        buf = self._bufs.get(env)
+        if buf is None:
+            env.seed_actions(self.seed)
+            self._bufs[env] = env._arng
+        elif env._arng is not buf:
+            env._attach_action_rng(buf)
+        return obj
+
+
+def _rollout_mlp_sample(env, agent, K, obs, rewards, actions, metrics, obs0, raw=False, log_prob=False):
+    """The closed loop of a GaussianMLPPolicyAgent: one invsim_rollout_mlp_sample call."""
+    if obs0 is None:
+        raise ValueError("a GaussianMLPPolicyAgent rollout needs obs0, the observation the env last returned "
+                         "(reset()'s, or the last row of the previous rollout's obs)")
+    N, dev, A = env.num_envs, env.device, env.action_dim
+    obs0 = torch.as_tensor(obs0, device=dev)
+    if tuple(obs0.shape) != (N, env.obs_dim):
+        raise ValueError(f"obs0 must have shape {(N, env.obs_dim)}, got {tuple(obs0.shape)}")
+    obs0 = obs0.to(env.obs_dtype).contiguous()
+    metrics = env._metrics_arg(metrics)
+    obj = agent.device_object(env)
+    out = {}
+    o = torch.empty((K, N, env.obs_dim), dtype=env.obs_dtype, device=dev) if obs else None
+    if rewards:
+        out["reward"] = torch.empty((K, N), dtype=torch.float64, device=dev)
+        out["terminated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+        out["truncated"] = torch.empty((K, N), dtype=torch.bool, device=dev)
+    a = torch.empty((K, N, A), dtype=env.act_dtype, device=dev) if actions else None
+    r = torch.empty((K, N, A), dtype=torch.float32, device=dev) if raw else None
+    lp = torch.empty((K, N), dtype=torch.float32, device=dev) if log_prob else None
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _capi.check(env._lib.invsim_rollout_mlp_sample(
+        env._h, int(K), obj, obs0.data_ptr(), p(o), p(out.get("reward")), p(out.get("terminated")),
+        p(out.get("truncated")), p(a), p(r), p(lp), p(metrics), env._stream()), env._h, "rollout_mlp_sample")
+    for key, t in (("obs", o), ("actions", a), ("raw_actions", r), ("log_prob", lp)):
+        if t is not None:
+            out[key] = t
+    return out
+
+
+def collect_rollout(env, agent, K, obs0, metrics=None):
+    """K steps of every env under a ``GaussianMLPPolicyAgent``, everything an
+    on-policy rollout buffer stores, from one C call (two launches per step,
+    no Python in the loop).  Returns device tensors: ``obs`` [K, N, O] (row k is
+    the observation after step k; the network's input at step k is ``obs0`` /
+    row k - 1), ``actions`` [K, N, A] (action dtype, what the env was stepped
+    with), ``raw_actions`` [K, N, A] and ``log_prob`` [K, N] float32 (the
+    unclipped sample and its log-density), ``reward`` [K, N] float64,
+    ``terminated`` / ``truncated`` [K, N] bool.  ``metrics`` as in
+    ``rollout_policy``.  Values are the caller's: one batched critic call over
+    ``obs``."""
+    if not isinstance(agent, GaussianMLPPolicyAgent):
+        raise TypeError("collect_rollout needs a GaussianMLPPolicyAgent")
+    return _rollout_mlp_sample(env, agent, int(K), True, True, True, metrics, obs0, raw=True, log_prob=True)
+
+
 def _rollout_mlp(env, agent, K, obs, rewards, actions, metrics, obs0):
     """The closed loop of an MLPPolicyAgent: one invsim_rollout_mlp call."""
     if obs0 is None:
@@ -635,11 +750,15 @@ def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metric
     the requested device tensors; ``metrics`` (float64 [N, M]) is accumulated in
     place when given.  The heuristic agents run in the step kernel, one launch;
     a ``TorchPolicyAgent`` runs in torch between K one-step launches and an
-    ``MLPPolicyAgent`` in a kernel of its own before each; both need ``obs0``,
+    ``MLPPolicyAgent`` in a kernel of its own before each (a
+    ``GaussianMLPPolicyAgent``: the sampling variant of that kernel; the
+    log-probabilities come with ``collect_rollout``); all need ``obs0``,
     the observation the env last returned (``actions`` then records what the
     policy produced at every step, reset steps included)."""
     if isinstance(agent, TorchPolicyAgent):
         return _rollout_torch(env, agent, int(K), obs, rewards, actions, metrics, obs0)
+    if isinstance(agent, GaussianMLPPolicyAgent):
+        return _rollout_mlp_sample(env, agent, int(K), obs, rewards, actions, metrics, obs0)
     if isinstance(agent, MLPPolicyAgent):
         return _rollout_mlp(env, agent, int(K), obs, rewards, actions, metrics, obs0)
     spec, keep = agent.device_spec(env)
@@ -712,7 +831,8 @@ def evaluate_agent(agent, env_cls, env_config=None, n_episodes=100, seed_offset=
     """Batched evaluate_agent: episode i = env i seeded seed_offset + i, one
     full episode under ``agent`` in one kernel launch (a ``TorchPolicyAgent``:
     one launch per step, with the policy's torch ops between; an
-    ``MLPPolicyAgent``: two launches per step, issued by the library).  Returns a dict of
+    ``MLPPolicyAgent`` or ``GaussianMLPPolicyAgent``: two launches per step, issued by
+    the library; the latter samples its actions).  Returns a dict of
     per-episode columns (the reference's summary DataFrame columns).
 
     Under torch.distributed (one process per GPU) the episodes are sharded by

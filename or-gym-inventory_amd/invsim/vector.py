@@ -345,6 +345,26 @@ class InvSimVectorEnv:
                     self._h, "mlp_actions")
         return (a, r) if raw else a
 
+    def mlp_sample(self, agent, obs):
+        """One sampling launch of a GaussianMLPPolicyAgent on obs [N, O]: a dict
+        with "actions" [N, A] (action dtype), "raw_actions" and "mean" [N, A]
+        float32 (the sample before conversion, the network's output) and
+        "log_prob" [N] float32.  Every env's action generator advances by A
+        normals; env state is not touched."""
+        o = torch.as_tensor(obs, device=self.device)
+        if tuple(o.shape) != (self.num_envs, self.obs_dim):
+            raise ValueError(f"obs must have shape {(self.num_envs, self.obs_dim)}, got {tuple(o.shape)}")
+        o = o.to(self.obs_dtype).contiguous()
+        obj = agent.device_object(self)
+        N, A = self.num_envs, self.action_dim
+        out = {"actions": self._alloc(N, A, dtype=self.act_dtype), "raw_actions": self._alloc(N, A, dtype=torch.float32),
+               "mean": self._alloc(N, A, dtype=torch.float32), "log_prob": self._alloc(N, dtype=torch.float32)}
+        _capi.check(self._lib.invsim_mlp_sample(self._h, obj, o.data_ptr(), out["actions"].data_ptr(),
+                                                out["raw_actions"].data_ptr(), out["mean"].data_ptr(),
+                                                out["log_prob"].data_ptr(), self._stream()),
+                    self._h, "mlp_sample")
+        return out
+
     # -- RandomAgent's action stream (include/invsim.h "RandomAgent") ----------
     def _action_high(self):
         """The action space's upper bounds in the action dtype (host array)."""
