@@ -364,29 +364,7 @@ int finish_create(invsim_handle *h, invsim_handle **out, int rc) {
     return INVSIM_OK;
 }
 
-
-// Host table of PTRS's right-hand side  -lam + k*log(lam) - loggam(k+1)  for the
-// k that occur in practice (lam +- 12 sd), evaluated with the host libm exactly as
-// numpy evaluates it (distributions.c random_poisson_ptrs).  The device looks it
-// up instead of computing a log-gamma per rejection test; k outside falls back.
-void rhs_table(PtrsConst &c, std::vector<double> &tab) {
-    c.k0 = 0;
-    c.nk = 0;
-    c.toff = (int32_t)tab.size();
-    if (!(c.lam >= 10) || c.lam > 1e8) return;
-    const double sd = std::sqrt(c.lam);
-    int64_t k0 = std::max<int64_t>(0, (int64_t)std::floor(c.lam - 12 * sd - 10));
-    const int64_t k1 = (int64_t)std::ceil(c.lam + 12 * sd + 40);
-    int64_t n = k1 - k0;
-    if (n > RHS_LDS_MAX) {      // keep the central RHS_LDS_MAX entries (the rest: device)
-        k0 = std::max<int64_t>(0, (int64_t)std::floor(c.lam) - RHS_LDS_MAX / 2 + 20);
-        n = RHS_LDS_MAX;
-    }
-    for (int64_t k = k0; k < k0 + n; k++)
-        tab.push_back(-c.lam + (double)k * c.loglam - np_loggam((double)(k + 1)));
-    c.k0 = (int32_t)k0;
-    c.nk = (int32_t)n;
-}
+// (rhs_table, the host table of PTRS's right-hand side: ptrs_table.hpp)
 
 }  // namespace
 

@@ -470,7 +470,7 @@ __host__ __device__ inline int next_period(int t, int horizon, int autoreset, bo
 }
 
 constexpr int WAVE = 64;          // one-wave workgroups: LDS obs tile stored with 16-B coalesced rows
-constexpr int RHS_LDS_MAX = 512;  // PTRS RHS table entries per Poisson rate (staged in LDS)
+// (RHS_LDS_MAX, the PTRS RHS table entries per Poisson rate staged in LDS: ptrs_table.hpp)
 
 struct LgTab {    // loggam(k + 1) for k < RHS_LDS_MAX (Newsvendor's per-episode rate; see RhsTab)
     const double *lg;
