@@ -469,7 +469,12 @@ __device__ __forceinline__ bool im_step_regs(const ImParams &P, int64_t e, bool 
 // im_flush_pending's stores with the rows given (im_split_kernel's EARLY
 // order works them out during its load phase): R[i] to ring row srow[i] (< 0:
 // no ring store, L_i = 0), the requested orders to action_log slot wslot (with
-// the int64 side ring for entries >= 2^32 - 1).  im_flush_pending keeps its
+// the int64 side ring for entries >= 2^32 - 1).  The stores are streamed
+// (kernels.hpp wt_store), so each is whole lines per wave instruction: a ring
+// row 8 B per lane, the action_log row as one store of the env's whole row
+// (12 B per lane at M1 = 3, 768 contiguous bytes per wave), the sentinel
+// already in place; the side ring's entries, single words of a line under
+// their own exec mask, follow as cached stores.  im_flush_pending keeps its
 // own body: built on this helper, the run and rollout kernels that use it came
 // out with other register and spill figures.  A change to the ring layout has
 // to reach both.
@@ -479,14 +484,22 @@ __device__ __forceinline__ void im_store_rows(int64_t *Rring, uint32_t *alog32, 
                                               const int64_t (&req)[M1], int64_t e) {
 #pragma unroll
     for (int i = 0; i < M1; i++)
-        if (srow[i] >= 0) st_store(Rring + (int64_t)srow[i] * S + e, R[i]);
+        if (srow[i] >= 0) wt_store(Rring + (int64_t)srow[i] * S + e, R[i]);
     if (D > 0) {
+        uint32_t lo[M1];
+        bool wide = false;
 #pragma unroll
         for (int i = 0; i < M1; i++) {
-            const int64_t idx = ((int64_t)wslot * S + e) * M1 + i;
-            const bool wide = req[i] >= (int64_t)IM_WIDE;
-            st_store(alog32 + idx, wide ? IM_WIDE : (uint32_t)req[i]);
-            if (wide) st_store(alog + idx, req[i]);
+            const bool w = req[i] >= (int64_t)IM_WIDE;
+            lo[i] = w ? IM_WIDE : (uint32_t)req[i];
+            wide |= w;
+        }
+        const int64_t idx = ((int64_t)wslot * S + e) * M1;
+        wt_store_row<M1>(alog32 + idx, lo);
+        if (wide) {   // rare, and single words of a line: cached (the row above holds IM_WIDE for them)
+#pragma unroll
+            for (int i = 0; i < M1; i++)
+                if (lo[i] == IM_WIDE) st_store(alog + idx + i, req[i]);
         }
     }
 }
@@ -844,8 +857,18 @@ __device__ __forceinline__ void wg_lds_sync() {
 // form the addresses of its up-front loads; as leading scalar parameters they
 // are in SGPRs when the wave starts (kernarg preload), so its first vector
 // loads wait for no scalar load.  A struct parameter is never preloaded, hence
-// no struct here.  In front of those loads the kernel reads no P field, no
-// value behind a pointer and no blockDim / gridDim (the hidden argument block).
+// no struct here.  In front of those loads the source uses no P field on the
+// packed path, no value behind a pointer and no blockDim / gridDim (the hidden
+// argument block).  The generated code still has one scalar-memory wait
+// there: `hot ? f(hw) : g(P, t, n, nw)` below is compiled to selects, so every
+// wave issues the s_loads of P.lt_max, t and n / nw at entry and waits for
+// them (s_waitcnt lgkmcnt(0)) before the first select.  Writing the two
+// derivations as two branches was measured and not kept: the loads of t and
+// n / nw stay at entry (later code needs them), the register allocator puts a
+// packed-path value into the unused fourth dword of their destination, and
+// the wait moves into the packed arm; headline +0.1 % alone, -0.6 % on top of
+// the streamed state stores, both inside the spread
+// (profiles/state_writeback/table.md).
 //   act, Ip, Bp, Rr, a32   io.act, P.I, P.B, P.Rring, P.alog32
 //   Acur                   the current lookahead slot (P.ahead + cur * 4 * Npad), or null
 //   n32                    N (the row stride follows: pad_n); the lookahead
@@ -877,6 +900,14 @@ constexpr int im_split_waves(int m1, bool npd, bool ahead, bool counter) {
 // tried).  !EARLY is the order the kernel always had.  The inline-draw step
 // (!AHEAD, once after a seed or a set_state) keeps it at every size.
 // profiles/early_stores/table.md
+// The EARLY instantiations also stream the state they store early (wt_store:
+// the dynamics wave's ring rows, action_log row, I and B, and the lookahead
+// workgroups' rows of the next slot), which are issued around the middle of
+// the wave's span and so can leave L2 before the kernel ends; 7.6 MB less to
+// write back at the end of the headline's launch, +3.7 % on the step.
+// Nothing in the launch reads these rows after they are written, and the
+// next launch reads them from memory whichever XCD it runs on.
+// profiles/state_writeback/table.md
 constexpr int IM_EARLY_STORES_MIN_N = 32768;
 template <int M1, bool BACKLOG, bool NPD, bool AHEAD, class RG = Pcg, bool EARLY = false>
 __global__ void __launch_bounds__(2 * WAVE)
@@ -918,6 +949,12 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
 #endif
         return x < 0 ? 0 : x;
     };
+    // the lookahead workgroups' stores into the next slot: streamed in the EARLY
+    // instantiations (kernels.hpp wt_store: 8 bytes per lane, whole lines per wave)
+    auto la_store = [](uint64_t *p, uint64_t v) {
+        if constexpr (EARLY) wt_store(p, v);
+        else st_store(p, v);
+    };
     // DEC: with the lookahead the dynamics wave loads d itself and the waves
     // meet once (tile complete); otherwise d is handed over at a first barrier
     constexpr bool DEC = AHEAD;
@@ -939,7 +976,7 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
             uint64_t u32 = 0;
             ts.flush((int)(threadIdx.x & (WAVE - 1)));
             const int64_t dn = draw(g, u32);
-            if (valid) st_store(anxt() + 2 * S + e, (uint64_t)dn);
+            if (valid) la_store(anxt() + 2 * S + e, (uint64_t)dn);
             return;
         }
         // the slot's rows first: their addresses come from the leading arguments
@@ -969,10 +1006,10 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
         TPROBE(2);
         if (valid) {
             uint64_t *const Anxt = anxt();
-            st_store(Anxt + e, g.hi);
-            st_store(Anxt + S + e, g.lo);
-            st_store(Anxt + 2 * S + e, (uint64_t)dn);
-            if (NPD) st_store(Anxt + 3 * S + e, u32);
+            la_store(Anxt + e, g.hi);
+            la_store(Anxt + S + e, g.lo);
+            la_store(Anxt + 2 * S + e, (uint64_t)dn);
+            if (NPD) la_store(Anxt + 3 * S + e, u32);
         }
         TWAIT();
         TPROBE(5);
@@ -1204,17 +1241,18 @@ im_split_kernel(const int64_t *act, int64_t *Ip, int64_t *Bp, const int64_t *Rr,
     };
     if constexpr (EARLY) {
         // The state stores in front of the tile barrier (see ImPending): each is
-        // whole 128-byte lines from one wave instruction, and the wave would
-        // otherwise idle here until the window wave's rows have landed.
+        // whole 128-byte lines from one wave instruction (streamed: wt_store),
+        // and the wave would otherwise idle here until the window wave's rows
+        // have landed.
         // Nothing between here and the tile copy writes a register they read.
         if (valid) {
             im_store_rows<M1>(const_cast<int64_t *>(Rr), const_cast<uint32_t *>(a32), alogw, S, D, srow, wslot, R, req,
                               e);   // Rr, a32: P.Rring, P.alog32
 #pragma unroll
-            for (int i = 0; i < M1; i++) st_store(Ip + i * S + e, Icur[i]);   // :326
+            for (int i = 0; i < M1; i++) wt_store(Ip + i * S + e, Icur[i]);   // :326
             if (BACKLOG) {
 #pragma unroll
-                for (int q = 0; q <= M1; q++) st_store(Bp + q * S + e, U[q]);   // :307-312
+                for (int q = 0; q <= M1; q++) wt_store(Bp + q * S + e, U[q]);   // :307-312
             }
             out_store(io.term + e, (uint8_t)0);
             out_store(io.trunc + e, (uint8_t)(trunc ? 1 : 0));   // :350

@@ -543,7 +543,7 @@ struct TableStage {
 // reads them in a later kernel or on the host, and streaming them past L2 leaves
 // less dirty data for the end-of-kernel write-back (measured on MI355X: +7 %
 // step, +15 % rollout throughput for InvMgmt).  State stores (st_store) stay
-// cached.
+// cached, except those a launch issues early (wt_store below).
 template <typename V>
 __device__ __forceinline__ void out_store(V *p, V v) {
     __builtin_nontemporal_store(v, p);
@@ -551,6 +551,42 @@ __device__ __forceinline__ void out_store(V *p, V v) {
 template <typename V>
 __device__ __forceinline__ void st_store(V *p, V v) {
     *p = v;
+}
+// State stores issued early in a launch (im_split_kernel's EARLY order: the
+// dynamics wave's rows in front of the tile barrier, the lookahead workgroups'
+// next-slot rows): streamed like the outputs, so that the bytes can leave L2
+// beside the tile stores that follow, not as dirty lines at the kernel's end
+// (116 B per env-step of the headline; measured on MI355X: +3.7 % step,
+// profiles/state_writeback/table.md).  Nothing reads them back in the launch
+// that wrote them.  For stores that are a wave's last instructions it makes
+// no difference (they drain at the end either way), so the late order and
+// the multi-step kernels keep st_store.  Rule: one wave
+// instruction has to cover whole 128-byte lines (every lane valid, the lanes'
+// bytes contiguous); a line streamed out in pieces is written once per piece.
+// Stores that cannot keep the rule (exec-guarded fix-ups) stay st_store.
+template <typename V>
+__device__ __forceinline__ void wt_store(V *p, V v) {
+    __builtin_nontemporal_store(v, p);
+}
+// A lane's row of M 32-bit words as the widest stores that cover it whole (one
+// of 4 * M bytes for M <= 4; 4-byte aligned, as a row of 3 words is)
+template <int W>
+struct WtWords {
+    typedef uint32_t V __attribute__((ext_vector_type(W)));
+    typedef V U __attribute__((aligned(4)));
+};
+template <int M, int O = 0>
+__device__ __forceinline__ void wt_store_row(uint32_t *p, const uint32_t (&v)[M]) {
+    constexpr int W = M - O >= 4 ? 4 : M - O;
+    if constexpr (W == 1) {
+        wt_store(p + O, v[O]);
+    } else {
+        typename WtWords<W>::V x;
+#pragma unroll
+        for (int i = 0; i < W; i++) x[i] = v[O + i];
+        __builtin_nontemporal_store(x, reinterpret_cast<typename WtWords<W>::U *>(p + O));
+    }
+    if constexpr (O + W < M) wt_store_row<M, O + W>(p, v);
 }
 
 // Copy `count` elements of an LDS tile to global memory, 16 B per lane.
