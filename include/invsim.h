@@ -96,7 +96,11 @@ typedef struct {
     const float *demand_cost;        /* [m] = k */
     const float *holding_cost;       /* [m] = append(h, 0) */
     const int64_t *supply_capacity;  /* [m-1] = c */
-    const int64_t *lead_time;        /* [m-1] = L, each 0..255 */
+    const int64_t *lead_time;        /* [m-1] = L, each 0..255, and the observation length
+                                        (m-1) * (max(L) + 1) <= 311: a wave's window tile
+                                        (512 B per entry), the 4 KiB PTRS table and the split
+                                        step's 512 B must fit the 160 KiB LDS of a workgroup
+                                        (else INVSIM_ERANGE, before any device call) */
     const int64_t *user_D;           /* [periods], dist == 5 only (else NULL) */
     int64_t dist_n;                  /* dist 2: dist_param['n'] */
     double dist_p;                   /* dist 2, 4: dist_param['p'] */

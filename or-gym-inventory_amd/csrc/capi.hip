@@ -490,6 +490,16 @@ int invsim_create_invmgmt(const invsim_invmgmt_spec *s, int64_t n, int32_t devic
     } else {
         return fail(nullptr, INVSIM_EINVAL, "dist must be one of 1, 2, 3, 4, 5");
     }
+    int D = 0, sumL = 0;
+    for (int i = 0; i < m1; i++) {
+        D = std::max<int>(D, (int)s->lead_time[i]);
+        sumL += (int)s->lead_time[i];
+    }
+    // the largest dynamic LDS a launch of this handle asks (the split step's: a
+    // wave's obs window tile, the PTRS table, one int64 per lane): with 160 KiB
+    // that is an observation length (m-1)*(max(L)+1) of at most 311
+    if (im_split_lds_bytes(m1, D) > LDS_LIMIT_BYTES)
+        return fail(nullptr, INVSIM_ERANGE, "observation length (m-1)*(max(L)+1) too large for the LDS window tile (at most 311)");
     DeviceGuard g(device);
     if (!g.ok) return fail(nullptr, INVSIM_EDEVICE, "hipSetDevice failed");
     auto *h = new invsim_handle();
@@ -497,17 +507,8 @@ int invsim_create_invmgmt(const invsim_invmgmt_spec *s, int64_t n, int32_t devic
     h->device = device;
     h->N = n;
     h->Npad = pad_n(n);
-    int D = 0, sumL = 0;
-    for (int i = 0; i < m1; i++) {
-        D = std::max<int>(D, (int)s->lead_time[i]);
-        sumL += (int)s->lead_time[i];
-    }
     h->obs_dim = m1 * (D + 1);
     h->act_dim = m1;
-    if (h->obs_dim > 320) {
-        delete h;
-        return fail(nullptr, INVSIM_ERANGE, "observation length (m-1)*(max(L)+1) > 320 not supported");
-    }
     h->im_m1 = m1;
     h->im_backlog = s->backlog != 0;
     Layout lay;

@@ -2226,13 +2226,10 @@ using ImRunModes = Values<Run::POLICY>;
 #else
 using ImRunModes = Values<Run::STEP, Run::STEPS, Run::POLICY>;
 #endif
-inline size_t im_run_lds_bytes(const ImParams &p, int M1) {   // the obs window tile and the PTRS table
-    return (size_t)EPW * M1 * (p.lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
-}
 template <class RG>
 hipError_t im_run_kernel_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
                                 const StepIO<int64_t, int64_t> &io, hipStream_t s) {
-    const size_t lds = im_run_lds_bytes(p, M1);
+    const size_t lds = im_run_lds_bytes(M1, p.lt_max);
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
     const PolicyIO &pv = pol_or_none(pol);
     const bool npd = p.dist >= 2 && p.dist <= 4;
@@ -2278,7 +2275,7 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
         return ce;
     };
     if (im_split_applies(p, t_u, pol, io)) {
-        const size_t lds2 = im_run_lds_bytes(p, M1) + WAVE * sizeof(int64_t);
+        const size_t lds2 = im_split_lds_bytes(M1, p.lt_max);
         ImParams q = p;
         if (!p.cm.kn.im_ahead) q.ahead = nullptr;
         if (!ph && la.valid && !q.ahead) {      // lookahead switched off: commit, then draw inline

@@ -758,6 +758,14 @@ hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const
 // cm.rng <- the committed generator state held by the lookahead cache (whose
 // current slot is `slot`); needed before anything reads cm.rng while it is valid
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s);
+// The dynamic LDS of the kernels whose request grows with the spec: im_run_kernel
+// (the obs window tile of a wave's envs and the PTRS table) and im_split_kernel
+// (one more int64 per lane).  The launchers ask for these; create refuses a
+// spec whose larger one is past the LDS a workgroup can have (launch.hpp).
+inline size_t im_run_lds_bytes(int M1, int lt_max) {
+    return (size_t)EPW * M1 * (lt_max + 1) * sizeof(int64_t) + RHS_LDS_MAX * sizeof(double);
+}
+inline size_t im_split_lds_bytes(int M1, int lt_max) { return im_run_lds_bytes(M1, lt_max) + WAVE * sizeof(int64_t); }
 
 // Compile-time specialised NetInvMgmt kernels for the reference's own graphs
 // (netspec.hip): which built-in topology a spec equals, and its launcher.

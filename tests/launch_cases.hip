@@ -13,6 +13,9 @@
 //   launch_cases nv|im|net          the reduced table (tests/golden/launch_choice_*.txt)
 //   launch_cases nv|im|net --full   every case of the product
 //
+// (im prints a second table after the first, with a count and hash of its own:
+// the specs at the ends of the range create accepts.)
+//
 // The product per family: stream x autoreset x t_u x K x io.obs x lookahead
 // before the call x policy x (settings + shapes), where a setting is the
 // default shape with one knob flipped, or a knob / N pair on either side of a
@@ -32,6 +35,7 @@
 // output.
 #include "kernels.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -211,7 +215,7 @@ struct ImShape {
     int M1, backlog, dist, lt_max, periods;
     int L[IM_MAX_M1];
 };
-void run_im(Out &out) {
+void run_im(Out &out, bool limits) {
     std::vector<Setting> sets = {setting("-"), setting("N0", 0)};
     auto flip = [&](const char *n, bool Knobs::*f) {
         Setting s = setting(n);
@@ -263,8 +267,29 @@ void run_im(Out &out) {
             add("m3ap", 3, 10, AP_LDS, {1, 5, 10});
             add("m8", 8, 4, 30, {1, 2, 3, 4, 1, 2, 3, 4});
         }
+    // the specs of tests/limit_cases.py at the ends of what create accepts (a
+    // table of their own, after the first: its lines record their kernels and
+    // LDS bytes); above_64k also past the EARLY threshold
+    std::vector<ImShape> lim;
+    for (int backlog = 0; backlog < 2; backlog++) {
+        auto add = [&](const char *n, int lt_max, int periods, std::initializer_list<int> L) {
+            ImShape s{n, (int)L.size(), backlog, 1, lt_max, periods, {}};
+            int i = 0;
+            for (int l : L) s.L[i++] = l;
+            lim.push_back(s);
+        };
+        add("L255", 255, 300, {255});
+        add("all_zero", 0, 9, {0, 0, 0, 0, 0, 0, 0, 0});
+        add("od_max_4", 102, 120, {17, 102, 0});
+        add("od_max_6", 61, 70, {61, 0, 1, 60, 5});
+        add("od_max_9", 37, 45, {37, 0, 1, 36, 5, 37, 2, 9});
+        add("above_64k", 40, 50, {17, 40, 3});
+    }
     const int pols[] = {POL_NONE, POL_CONSTANT, POL_BASE_STOCK, POL_SS, POL_RANDOM, POL_EXTERNAL, POL_LEVELS};
-    std::vector<double> ap(AP_LDS + 2);
+    int max_periods = 0;   // ap_host is read at t_u <= periods
+    for (const ImShape &sh : shapes) max_periods = std::max(max_periods, sh.periods);
+    for (const ImShape &sh : lim) max_periods = std::max(max_periods, sh.periods);
+    std::vector<double> ap(max_periods + 2);
     for (size_t i = 0; i < ap.size(); i++) ap[i] = 1.0 / (double)(i + 1);
     auto one = [&](const Setting &st, const ImShape &sh) {
         for_axes([&](const Axes &a) {
@@ -302,6 +327,12 @@ void run_im(Out &out) {
             }
         });
     };
+    if (limits) {
+        for (const ImShape &sh : lim) one(setting("-"), sh);
+        for (const ImShape &sh : lim)
+            if (sh.name == "above_64k") one(setting("N=early_min+1", EARLY_N + 1), sh);
+        return;
+    }
     for (const Setting &st : sets)
         for (const ImShape &sh : shapes)
             if (sh.name == "m3" && sh.dist == 1) one(st, sh);   // the settings: the default shape, both backlog modes
@@ -380,7 +411,15 @@ int main(int argc, char **argv) {
     if (argc < 2) return 2;
     Out out{argc > 2 && !strcmp(argv[2], "--full")};
     if (!strcmp(argv[1], "nv")) run_nv(out);
-    else if (!strcmp(argv[1], "im")) run_im(out);
+    else if (!strcmp(argv[1], "im")) {
+        run_im(out, false);
+        out.end();
+        if (!out.full) puts("# the limit specs");
+        Out lim{out.full};
+        run_im(lim, true);
+        lim.end();
+        return 0;
+    }
     else if (!strcmp(argv[1], "net")) run_net(out);
     else return 2;
     out.end();

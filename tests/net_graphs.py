@@ -22,6 +22,8 @@ minimal    raw -> retailer -> market, L = 0: J = E = RL = 1, obs_dim = 2
 chain      raw -> four distributors in series -> markets, no factory
 wide       20 main nodes in layers, 44 reorder links, 6 market links: the
            kernel's dynamic LDS request is above 64 KB and below 160 KB
+series     raw -> n distributors in series -> market, every link with lead
+           time L (the create-time limits, tests/limit_cases.py)
 too_large  24 main nodes, 60 reorder links: inside the J / E / RL limits, LDS
            need above 160 KB (creation must fail)
 """
@@ -187,6 +189,17 @@ def too_large(sampler=by_name, T=8):
     256 / 64): the LDS scratch plus the obs tile need more than 160 KB."""
     return _layered(sampler, T, widths=(4, 8, 8, 4), fanin=(2, 2, 5), leads=(2, 1, 3, 2, 3, 2, 1, 3, 1),
                     n_lateral=2, n_feed=2)
+
+
+def series(n_main, L=1):
+    """raw -> n_main distributors in series -> market"""
+    g = nx.DiGraph()
+    g.add_nodes_from([0, 1])
+    for j in range(2, 2 + n_main):
+        g.add_nodes_from([j], I0=5, h=0.01)
+        g.add_edge(j - 1, j, L=L, p=1.1, g=0.001)
+    g.add_edge(1 + n_main, 0, p=2.3, b=0.1, demand_dist_func="poisson", dist_param={"lam": 2})
+    return g
 
 
 GRAPHS = {"mixed": mixed, "minimal": minimal, "chain": chain, "wide": wide, "too_large": too_large}

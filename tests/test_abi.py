@@ -114,6 +114,42 @@ def test_validation_errors_mirror_reference_asserts():
         assert msg in lib.invsim_last_error(None)
 
 
+@pytest.mark.parametrize("stages", [4, 6, 9])
+def test_invmgmt_create_refuses_what_the_lds_cannot_hold(stages):
+    """The largest observation length of each stage count whose launches fit the
+    160 KiB of LDS passes validation (it then fails on the device here, or makes
+    a handle where there is one); one more period of lead time is refused with
+    INVSIM_ERANGE before any device call (tests/limit_cases.py OD_MAX / OD_REFUSED)."""
+    import numpy as np
+    import limit_cases as lc
+    from invsim import _capi
+    lib = _capi.load_library()
+    m1 = stages - 1
+    I0, c = np.full(m1, 100, np.int64), np.full(m1, 100, np.int64)
+    f = np.ones(stages, np.float32)
+
+    def create(L, periods):
+        L = np.array(L, np.int64)
+        spec = _capi.InvMgmtSpec(stages, periods, 1, 1, 20.0, 0.97, I0.ctypes.data, f.ctypes.data, f.ctypes.data,
+                                 f.ctypes.data, f.ctypes.data, c.ctypes.data, L.ctypes.data, None)
+        h = C.c_void_p()
+        rc = lib.invsim_create_invmgmt(C.byref(spec), 8, 0, 0, C.byref(h))
+        msg = lib.invsim_last_error(None)
+        if rc == 0:
+            lib.invsim_destroy(h)
+        return rc, msg
+
+    L_ok, periods = lc.OD_MAX[stages]
+    rc, msg = create(L_ok, periods)
+    assert rc in (0, -5), (rc, msg)              # INVSIM_OK, or INVSIM_EDEVICE without a GPU: past the validation
+    rc, msg = create(lc.OD_REFUSED[stages], periods)
+    assert rc == -34 and b"LDS" in msg, (rc, msg)
+    # the bound is the LDS, not a length of its own: 320 entries, the old bound, is refused as well
+    if stages == 6:
+        rc, msg = create((63, 0, 1, 62, 5), periods)
+        assert rc == -34 and b"LDS" in msg, (rc, msg)
+
+
 def test_python_env_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -11,7 +11,6 @@ demands.  References: the goldens recorded from the reference env, the C
 oracle at 197 envs (three full 64-env groups and a group of 5), the cohort
 oracle for staggered periods, oracle/agents.py for the in-kernel policy.
 """
-import networkx as nx
 import numpy as np
 import pytest
 import torch
@@ -305,15 +304,7 @@ def _still_works(gpu, oracle):
     _eq(_np(r), e_r, "reward after a refused create")
 
 
-def _series(n_main, L=1):
-    """raw -> n_main distributors in series -> market"""
-    g = nx.DiGraph()
-    g.add_nodes_from([0, 1])
-    for j in range(2, 2 + n_main):
-        g.add_nodes_from([j], I0=5, h=0.01)
-        g.add_edge(j - 1, j, L=L, p=1.1, g=0.001)
-    g.add_edge(1 + n_main, 0, p=2.3, b=0.1, demand_dist_func="poisson", dist_param={"lam": 2})
-    return g
+_series = net_graphs.series
 
 
 def test_create_time_limits(gpu, oracle):
