@@ -444,6 +444,76 @@ int invsim_rollout_mlp_sample(invsim_handle *h, int32_t K, const invsim_mlp *m, 
                               void *obs, double *reward, uint8_t *terminated, uint8_t *truncated, void *actions,
                               float *raw /* [K][N][A] */, float *logp /* [K][N] */, double *metrics, void *stream);
 
+/* ---- Critic, GAE and parameter updates: what an on-policy iteration (PPO /
+ * A2C, the reference's benchmark_*_sb3_rllib.py) needs around the collected
+ * rollout, with no host synchronisation: values under the MLP actor's
+ * arithmetic, advantages as one backward scan, and new weights written into an
+ * existing object on the stream.
+ *
+ * Value networks.  invsim_mlp_create_value is invsim_mlp_create (same spec,
+ * same host-side validation, same blob) with these differences: dims[n_layers]
+ * must be 1 (INVSIM_ERANGE); clip must be 0 (INVSIM_EINVAL), low / high are
+ * ignored; out_scale / out_shift are [1] and de-normalise the value; no scratch
+ * rows are allocated.  invsim_mlp_destroy frees it.  invsim_mlp_values is the
+ * MLP actor's kernel through its raw output: values[r] is the "MLP actor"
+ * contract up to `output` on obs row r, and no conversion is applied.  `rows`
+ * is independent of the handle's N (one launch covers [K][N][O]); rows == 0
+ * is a no-op, rows < 0 INVSIM_EINVAL.  It does not touch env state and is legal
+ * inside a capture bracket.  A value object is refused (INVSIM_EINVAL) by
+ * invsim_mlp_actions, invsim_mlp_sample, invsim_mlp_set_gaussian,
+ * invsim_rollout_mlp and invsim_rollout_mlp_sample; an actor is refused by
+ * invsim_mlp_values; another handle's object is refused everywhere.
+ *
+ * GAE.  invsim_gae is handle-free, like invsim_episode_fold, and runs on the
+ * current device.  value0[n] is V of the observation the first step's network
+ * saw (obs0), values[k][n] V of obs row k, done0 terminated | truncated of the
+ * row just before this block (the previous call's last row; NULL: no env had
+ * just finished).  Per env n, for k = K - 1 down to 0, in f64 with every
+ * operation rounded separately (no fused multiply-add), carry = +0.0 at first:
+ *   done_k = terminated[k][n] | truncated[k][n]           (a NULL array reads 0)
+ *   prev   = k > 0 ? done_{k-1} : (done0 ? done0[n] != 0 : 0)
+ *   vp = (double)(k > 0 ? values[k-1][n] : value0[n]);   vn = (double)values[k][n]
+ *   if prev:      the row after a finished episode: NEXT_STEP's reset row, no transition
+ *       advantages[k][n] = +0.0f;  returns[k][n] = (float)vp;  valid = 0;  carry = +0.0
+ *   else:
+ *       b     = terminated[k][n] ? +0.0 : gamma * vn        truncation bootstraps from the final obs
+ *       delta = (reward[k][n] + b) - vp
+ *       adv   = done_k ? delta : delta + gl * carry         gl = gamma * lambda, one product on the host
+ *       carry = adv;  advantages[k][n] = (float)adv;  returns[k][n] = (float)(adv + vp);  valid = 1
+ * Under NEXT_STEP autoreset obs row k of a truncated step is the episode's
+ * final observation, so gamma * V(that row) is the truncation bootstrap; row
+ * k + 1 is the reset row (reward 0, action ignored by the env), which `valid`
+ * masks out of a loss.  K < 0 or n_envs < 0 is INVSIM_EINVAL; K == 0 or n_envs
+ * == 0 returns INVSIM_OK without a launch; otherwise a NULL reward, value0,
+ * values, advantages or returns is INVSIM_EINVAL.  NaN and infinite inputs
+ * propagate by the formulas; gamma and lambda are not range-checked.  One
+ * launch, no atomics: the result is deterministic.  Capturable.
+ *
+ * Parameter updates.  invsim_mlp_update enqueues one small launch on `stream`
+ * that rewrites the object's parameter blob from the caller's device arrays, in
+ * the layout invsim_mlp_create builds (transposed, zero padded: the padding
+ * stays zero); a NULL weight / bias entry, or a NULL array, keeps what the
+ * object has.  With std / log_std (device [A], both or neither: INVSIM_EINVAL)
+ * it also writes the Gaussian rows and sets the object's Gaussian, as
+ * invsim_mlp_set_gaussian does; on a value object std is INVSIM_EINVAL.  No
+ * allocation, no host copy, no synchronisation: launches on `stream` after it
+ * see the new parameters, and the caller orders it against launches on other
+ * streams.  Legal inside a capture bracket; a replay re-reads the caller's
+ * arrays as they are then.  The layer shapes are the object's: there is nothing
+ * to validate on the device, and the caller answers for finite std >= 0. */
+int invsim_mlp_create_value(invsim_handle *h, const invsim_mlp_spec *spec, invsim_mlp **out);
+int invsim_mlp_values(invsim_handle *h, const invsim_mlp *m, const void *obs /* [rows][O], obs dtype */,
+                      int64_t rows, float *values /* [rows] */, void *stream);
+int invsim_gae(const double *reward /* [K][n] */, const uint8_t *terminated, const uint8_t *truncated /* [K][n], either may be NULL */,
+               const uint8_t *done0 /* [n] or NULL */, const float *value0 /* [n] */, const float *values /* [K][n] */,
+               int32_t K, int64_t n_envs, double gamma, double lambda,
+               float *advantages /* [K][n] */, float *returns /* [K][n] */, uint8_t *valid /* [K][n], may be NULL */,
+               void *stream);
+int invsim_mlp_update(invsim_handle *h, invsim_mlp *m,
+                      const float *const *weight /* host array of n_layers DEVICE pointers, row-major [dims[l+1]][dims[l]] */,
+                      const float *const *bias /* likewise, [dims[l+1]] */, const float *std,
+                      const float *log_std /* DEVICE [A], both or neither */, void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

@@ -14,6 +14,7 @@
 #include "../../include/invsim.h"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "gae.hpp"
 #include "mlp_policy.hpp"
 
 using namespace invsim;
@@ -103,6 +104,7 @@ struct invsim_mlp {
     float *g_std = nullptr, *g_log_std = nullptr;
     bool gauss = false;
     float logp0 = 0.0f;         // (float)(-0.5 * log(2 pi) * A)
+    bool value = false;         // a value network (invsim_mlp_create_value): one output, no conversion, no scratch rows
 };
 
 namespace {
@@ -1233,19 +1235,22 @@ int invsim_rollout_metrics(invsim_handle *h, int32_t K, const void *actions, voi
 }
 
 // ------------------------------------------------------------------ MLP actor
-int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **out) {
+// invsim_mlp_create, and with `value` invsim_mlp_create_value: the same blob
+// with one output unit in place of the handle's action_dim
+static int mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **out, bool value) {
     if (!h || !sp || !out) return fail(h, INVSIM_EINVAL, "null argument");
     *out = nullptr;
     if (int rc = refuse_in_capture(h, "mlp_create")) return rc;
+    const int out_dim = value ? 1 : h->act_dim;
     const int n = sp->n_layers;
     if (n < 1 || n > INVSIM_MLP_MAX_LAYERS)
         return fail(h, INVSIM_ERANGE, "n_layers must be 1.." + std::to_string(INVSIM_MLP_MAX_LAYERS));
     if (!sp->dims || !sp->weight) return fail(h, INVSIM_EINVAL, "null dims / weight");
-    if (sp->dims[0] != h->obs_dim || sp->dims[n] != h->act_dim)
+    if (sp->dims[0] != h->obs_dim || sp->dims[n] != out_dim)
         return fail(h, INVSIM_ERANGE, "dims[0] / dims[n_layers] must be the handle's obs_dim " + std::to_string(h->obs_dim) +
-                                          " / action_dim " + std::to_string(h->act_dim));
+                                          (value ? " / 1 (a value network)" : " / action_dim " + std::to_string(out_dim)));
     if (h->obs_dim > INVSIM_MLP_MAX_WIDTH) return fail(h, INVSIM_ERANGE, "obs_dim too large for an MLP actor");
-    if (h->act_dim > INVSIM_POLICY_MAX_ACTION) return fail(h, INVSIM_ERANGE, "action_dim too large for an MLP actor");
+    if (out_dim > INVSIM_POLICY_MAX_ACTION) return fail(h, INVSIM_ERANGE, "action_dim too large for an MLP actor");
     for (int l = 1; l < n; l++)
         if (sp->dims[l] < 1 || sp->dims[l] > INVSIM_MLP_MAX_WIDTH)
             return fail(h, INVSIM_ERANGE, "hidden widths must be 1.." + std::to_string(INVSIM_MLP_MAX_WIDTH));
@@ -1255,6 +1260,7 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
         return fail(h, INVSIM_EINVAL, "out_activation must be INVSIM_MLP_NONE or INVSIM_MLP_TANH");
     if ((sp->in_scale == nullptr) != (sp->in_shift == nullptr) || (sp->out_scale == nullptr) != (sp->out_shift == nullptr))
         return fail(h, INVSIM_EINVAL, "scale and shift are given in pairs");
+    if (value && sp->clip) return fail(h, INVSIM_EINVAL, "a value network has no action bounds: clip must be 0");
     if (sp->clip && (!sp->low || !sp->high)) return fail(h, INVSIM_EINVAL, "clip needs the action bounds low / high");
     for (int l = 0; l < n; l++)
         if (!sp->weight[l]) return fail(h, INVSIM_EINVAL, "null weight matrix");
@@ -1262,9 +1268,10 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
     // one blob of 8-byte slots: per layer the transposed weights [in][opad] and the
     // bias [opad], then the scales and the bounds
     const bool i64 = h->family == INVSIM_INVMGMT;
-    const int O = h->obs_dim, A = h->act_dim;
+    const int O = h->obs_dim, A = out_dim;
     auto m = new invsim_mlp();
     m->owner = h;
+    m->value = value;
     MlpDev &d = m->dev;
     d.n_layers = n;
     d.act = n > 1 ? sp->activation : INVSIM_MLP_NONE;
@@ -1323,8 +1330,10 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
     const size_t n_el = (size_t)std::max<int64_t>(h->N, 1);
     hipError_t e = mlp_prepare();
     if (e == hipSuccess) e = hipMalloc(&m->blob, blob.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&m->obs_row, n_el * O * esz);
-    if (e == hipSuccess) e = hipMalloc(&m->act_row, n_el * A * esz);
+    if (!value) {        // the closed loop's scratch rows: a value network is never in that loop
+        if (e == hipSuccess) e = hipMalloc(&m->obs_row, n_el * O * esz);
+        if (e == hipSuccess) e = hipMalloc(&m->act_row, n_el * A * esz);
+    }
     if (e == hipSuccess) {
         const float *base = m->blob;
         for (int l = 0; l < n; l++) {
@@ -1351,6 +1360,23 @@ int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
     return INVSIM_OK;
 }
 
+int invsim_mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **out) {
+    return mlp_create(h, sp, out, false);
+}
+
+int invsim_mlp_create_value(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **out) {
+    return mlp_create(h, sp, out, true);
+}
+
+// what every call that takes an actor checks of its object
+static int mlp_actor_check(invsim_handle *h, const invsim_mlp *m) {
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (m->value)
+        return fail(h, INVSIM_EINVAL, "this invsim_mlp is a value network (invsim_mlp_create_value): it produces no "
+                                      "actions; evaluate it with invsim_mlp_values");
+    return INVSIM_OK;
+}
+
 void invsim_mlp_destroy(invsim_mlp *m) {
     if (!m) return;
     if (m->owner->capturing) {     // hipFree synchronises: the object stays valid
@@ -1365,11 +1391,56 @@ int invsim_mlp_actions(invsim_handle *h, const invsim_mlp *m, const void *obs, v
                        void *stream) {
     TraceRange tr_("invsim_mlp_actions");
     if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
-    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (int rc = mlp_actor_check(h, m)) return rc;
     if (h->N && !obs) return fail(h, INVSIM_EINVAL, "null obs");
     DeviceGuard g(h->device);
     hipError_t e = mlp_launch(m->dev, m->dev_copy, h->family == INVSIM_INVMGMT, obs, actions, raw, h->N, (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp launch");
+}
+
+int invsim_mlp_values(invsim_handle *h, const invsim_mlp *m, const void *obs, int64_t rows, float *values,
+                      void *stream) {
+    TraceRange tr_("invsim_mlp_values");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (!m->value)
+        return fail(h, INVSIM_EINVAL, "this invsim_mlp is an actor: a value network comes from invsim_mlp_create_value");
+    if (rows < 0) return fail(h, INVSIM_EINVAL, "rows must be >= 0");
+    if (rows == 0) return INVSIM_OK;
+    // the launch's grid is rows / 64 workgroups in one dimension; every index in the kernel is 64-bit
+    if (rows > (int64_t)INT32_MAX * MLP_ENVS) return fail(h, INVSIM_ERANGE, "too many rows for one launch");
+    if (!obs || !values) return fail(h, INVSIM_EINVAL, "null obs / values");
+    DeviceGuard g(h->device);
+    // the network kernel through its raw output: one unit per row, no conversion
+    hipError_t e = mlp_launch(m->dev, m->dev_copy, h->family == INVSIM_INVMGMT, obs, nullptr, values, rows, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp values launch");
+}
+
+int invsim_mlp_update(invsim_handle *h, invsim_mlp *m, const float *const *weight, const float *const *bias,
+                      const float *std, const float *log_std, void *stream) {
+    TraceRange tr_("invsim_mlp_update");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if ((std == nullptr) != (log_std == nullptr)) return fail(h, INVSIM_EINVAL, "std and log_std are given together");
+    if (std && m->value) return fail(h, INVSIM_EINVAL, "a value network has no Gaussian: std must be NULL");
+    const MlpDev &d = m->dev;
+    MlpUpdate u{};
+    u.n_layers = d.n_layers;
+    u.A = d.dims[d.n_layers];
+    for (int l = 0; l < d.n_layers; l++) {
+        u.in[l] = d.dims[l], u.out[l] = d.dims[l + 1], u.opad[l] = d.opad[l];
+        u.w_src[l] = weight ? weight[l] : nullptr;
+        u.b_src[l] = bias ? bias[l] : nullptr;
+        u.wt[l] = const_cast<float *>(d.wt[l]);         // into m->blob, which is ours to write
+        u.bias[l] = const_cast<float *>(d.bias[l]);
+    }
+    u.std_src = std, u.log_std_src = log_std;
+    u.std = m->g_std, u.log_std = m->g_log_std;
+    DeviceGuard g(h->device);
+    hipError_t e = mlp_update_launch(u, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, "mlp update launch");
+    if (std) m->gauss = true;
+    return INVSIM_OK;
 }
 
 // what the sampling launch needs beyond the network: a Gaussian on m and the
@@ -1387,7 +1458,7 @@ static int mlp_sample_args(invsim_handle *h, const invsim_mlp *m, MlpSample &sm)
 
 int invsim_mlp_set_gaussian(invsim_handle *h, invsim_mlp *m, const float *std, const float *log_std) {
     if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
-    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (int rc = mlp_actor_check(h, m)) return rc;
     if (int rc = refuse_in_capture(h, "mlp_set_gaussian")) return rc;
     if (!std) {
         m->gauss = false;
@@ -1416,7 +1487,7 @@ int invsim_mlp_sample(invsim_handle *h, const invsim_mlp *m, const void *obs, vo
                       float *logp, void *stream) {
     TraceRange tr_("invsim_mlp_sample");
     if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
-    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (int rc = mlp_actor_check(h, m)) return rc;
     if (h->N && !obs) return fail(h, INVSIM_EINVAL, "null obs");
     if (!actions && !raw && !mean && !logp) return fail(h, INVSIM_EINVAL, "no output: every output pointer is null");
     MlpSample sm{};
@@ -1436,7 +1507,7 @@ static int rollout_mlp(invsim_handle *h, int32_t K, const invsim_mlp *m, const v
     if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
     if (K < 0) return fail(h, INVSIM_EINVAL, "K must be >= 0");
     if (K == 0) return INVSIM_OK;
-    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (int rc = mlp_actor_check(h, m)) return rc;
     if (h->N && !obs0) return fail(h, INVSIM_EINVAL, "null obs0: the network's first input is the observation the env "
                                                      "last returned");
     if (int rc = metric_rollout_checks(h, reward, terminated, truncated)) return rc;
@@ -1579,6 +1650,19 @@ int invsim_episode_fold_groups(const double *reward, const uint8_t *terminated, 
         return fail(nullptr, INVSIM_EINVAL, "episode_fold_groups: null buffer or negative size");
     hipError_t e = episode_fold_groups_launch(reward, terminated, truncated, K, n_envs, ret, part, (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "episode_fold_groups launch");
+}
+
+int invsim_gae(const double *reward, const uint8_t *terminated, const uint8_t *truncated, const uint8_t *done0,
+               const float *value0, const float *values, int32_t K, int64_t n_envs, double gamma, double lambda,
+               float *advantages, float *returns, uint8_t *valid, void *stream) {
+    TraceRange tr_("invsim_gae");
+    if (K < 0 || n_envs < 0) return fail(nullptr, INVSIM_EINVAL, "gae: negative size");
+    if (K == 0 || n_envs == 0) return INVSIM_OK;
+    if (!reward || !value0 || !values || !advantages || !returns)
+        return fail(nullptr, INVSIM_EINVAL, "gae: null reward / value0 / values / advantages / returns");
+    hipError_t e = gae_launch(reward, terminated, truncated, done0, value0, values, K, n_envs, gamma, lambda, advantages,
+                              returns, valid, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "gae launch");
 }
 
 int invsim_set_episode_sink(invsim_handle *h, double *ret, double *part) {

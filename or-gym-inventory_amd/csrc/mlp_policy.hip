@@ -27,8 +27,10 @@
 namespace invsim {
 namespace {
 
-// The parameter blob is written once, before any launch, and only read by the
-// kernels: pointers into it are taken in the constant address space, so every
+// The parameter blob is written before a launch (at create, or by an earlier
+// mlp_update_kernel launch, whose stores are visible at this one's start) and
+// only read by the network kernels: pointers into it are taken in the constant
+// address space, so every
 // wave-uniform read of it (the argument block, weights, biases, output scales)
 // is a scalar load whatever the compiler can prove about aliasing.
 #define MLP_CONST __attribute__((address_space(4)))
@@ -196,7 +198,41 @@ __global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restric
 
 constexpr int MLP_LDS_MAX = 2 * MLP_WIDTH * MLP_ROW * (int)sizeof(float);   // 133 120 B of the CU's 160 KiB
 
+// invsim_mlp_update: blockIdx.y = layer (n_layers: the Gaussian rows), the
+// workgroups of a layer stride over its [in][opad] destination, so the stores
+// are contiguous and the (small, cache-resident) source is read transposed.
+// Every destination word is written: padding columns with +0.0f.
+constexpr int MLP_UPD_THREADS = 256, MLP_UPD_BLOCKS = 64;
+__global__ __launch_bounds__(MLP_UPD_THREADS) void mlp_update_kernel(MlpUpdate u) {
+    const int l = blockIdx.y, t0 = blockIdx.x * MLP_UPD_THREADS + threadIdx.x, stride = gridDim.x * MLP_UPD_THREADS;
+    if (l == u.n_layers) {
+        if (u.std_src)
+            for (int a = t0; a < u.A; a += stride) {
+                u.std[a] = u.std_src[a];
+                u.log_std[a] = u.log_std_src[a];
+            }
+        return;
+    }
+    const int in = u.in[l], out = u.out[l], opad = u.opad[l];
+    if (const float *w = u.w_src[l]) {
+        float *dst = u.wt[l];
+        for (int d = t0; d < in * opad; d += stride) {
+            const int i = d / opad, j = d - i * opad;
+            dst[d] = j < out ? w[j * in + i] : 0.0f;
+        }
+    }
+    if (const float *b = u.b_src[l]) {
+        float *dst = u.bias[l];
+        for (int j = t0; j < opad; j += stride) dst[j] = j < out ? b[j] : 0.0f;
+    }
+}
+
 }  // namespace
+
+hipError_t mlp_update_launch(const MlpUpdate &u, hipStream_t s) {
+    hipLaunchKernelGGL(mlp_update_kernel, dim3(MLP_UPD_BLOCKS, u.n_layers + 1), dim3(MLP_UPD_THREADS), 0, s, u);
+    return hipGetLastError();
+}
 
 hipError_t mlp_prepare() {
     const void *kernels[] = {(const void *)mlp_policy_kernel<true>, (const void *)mlp_policy_kernel<false>,

@@ -64,4 +64,22 @@ struct MlpSample {
 hipError_t mlp_sample_launch(const MlpDev &m, const MlpDev *dev, bool i64, const void *obs, void *actions, float *raw,
                              const MlpSample &sm, int64_t N, hipStream_t s);
 
+// invsim_mlp_update's by-value kernel argument (include/invsim.h "Critic, GAE
+// and parameter updates"): per layer the caller's row-major weight / bias
+// (device, null = keep) and where they go in the parameter blob.
+struct MlpUpdate {
+    int32_t n_layers, A;              // A: entries of std / log_std
+    int32_t in[MLP_LAYERS], out[MLP_LAYERS], opad[MLP_LAYERS];
+    const float *w_src[MLP_LAYERS];   // [out][in]
+    const float *b_src[MLP_LAYERS];   // [out]
+    float *wt[MLP_LAYERS];            // [in][opad]
+    float *bias[MLP_LAYERS];          // [opad]
+    const float *std_src, *log_std_src;   // [A], both or neither
+    float *std, *log_std;
+};
+
+// one launch: rewrites the blob's layers (padding columns get +0.0f again) and
+// the Gaussian rows; no allocation, copy or synchronisation
+hipError_t mlp_update_launch(const MlpUpdate &u, hipStream_t s);
+
 }  // namespace invsim

@@ -31,6 +31,8 @@ _LAZY = {
     "MLPPolicyAgent": "policies",
     "GaussianMLPPolicyAgent": "policies",
     "collect_rollout": "policies",
+    "ValueMLP": "policies",
+    "gae": "policies",
     "LevelsAgent": "policies",
     "NetLevelsAgent": "policies",
     "evaluate_levels": "policies",

@@ -33,6 +33,7 @@ EXPORTS = (
     "invsim_rollout_metrics",
     "invsim_mlp_create", "invsim_mlp_destroy", "invsim_mlp_actions", "invsim_rollout_mlp",
     "invsim_mlp_set_gaussian", "invsim_mlp_sample", "invsim_rollout_mlp_sample",
+    "invsim_mlp_create_value", "invsim_mlp_values", "invsim_gae", "invsim_mlp_update",
     "invsim_set_policy_levels", "invsim_set_policy_net_levels",
 )
 ABI_VERSION = 4
@@ -144,6 +145,10 @@ def _declare(lib):
         "invsim_mlp_set_gaussian": ([H, P, P, P], C.c_int),
         "invsim_mlp_sample": ([H, P, P, P, P, P, P, P], C.c_int),
         "invsim_rollout_mlp_sample": ([H, I32, P, P, P, P, P, P, P, P, P, P, P], C.c_int),
+        "invsim_mlp_create_value": ([H, P, P], C.c_int),
+        "invsim_mlp_values": ([H, P, P, I64, P, P], C.c_int),
+        "invsim_gae": ([P, P, P, P, P, P, I32, I64, C.c_double, C.c_double, P, P, P, P], C.c_int),
+        "invsim_mlp_update": ([H, P, P, P, P, P, P], C.c_int),
         "invsim_set_policy_levels": ([H, P, P], C.c_int),
         "invsim_set_policy_net_levels": ([H, P, P], C.c_int),
     }

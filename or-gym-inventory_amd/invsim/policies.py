@@ -50,7 +50,12 @@ two launches per step with no Python between them.  A
 ``GaussianMLPPolicyAgent`` is that actor with a diagonal Gaussian around it,
 sampled in the same kernel: ``collect_rollout`` returns what an on-policy
 learner (the scripts' SB3 ``PPO`` / ``A2C``) stores per step, log-probabilities
-included.
+included.  With ``critic=ValueMLP(...)`` it also evaluates the value network in
+the same kernel's arithmetic and computes the advantages in one launch (``gae``;
+truncation bootstraps from the final observation, NEXT_STEP reset rows are
+masked), and ``update_from_module`` writes the optimiser's new weights into the
+device copies on the stream (``include/invsim.h``, "Critic, GAE and parameter
+updates").
 
 ``evaluate_agent(agent, env_cls, env_config, n_episodes, seed_offset)`` returns
 the reference's summary columns (benchmark_InvManagementBacklogEnv.py:346-440,
@@ -538,15 +543,15 @@ class MLPPolicyAgent(_Agent):
         self.clip = bool(clip)
         self.name = name
         self._objs = weakref.WeakKeyDictionary()      # env -> (its handle, the invsim_mlp built for it)
+        self._live = None         # update_from_module: the device tensors the last update reads
+        self._updated = False     # the device copies no longer hold this object's host arrays
+
+    _value = False                # ValueMLP: one output unit, invsim_mlp_create_value
 
     @classmethod
-    def from_module(cls, module, **kw):
-        """From an ``nn.Sequential`` of ``Linear`` / ``ReLU`` / ``Tanh`` (SB3's
-        ``mlp_extractor.policy_net`` followed by ``action_net``, flattened into
-        one Sequential): a Linear, then activation and Linear alternating, an
-        optional activation at the end (which must be Tanh).  The parameters are
-        copied as float32.  Anything else, or two different hidden activations,
-        is a TypeError.  Other arguments go to the constructor."""
+    def _walk(cls, module):
+        """(layers, hidden activation, output activation) of an ``nn.Sequential``
+        of ``Linear`` / ``ReLU`` / ``Tanh``; TypeError for anything else."""
         nn = torch.nn
         if not isinstance(module, nn.Sequential):
             raise TypeError("from_module takes an nn.Sequential of Linear / ReLU / Tanh")
@@ -569,9 +574,20 @@ class MLPPolicyAgent(_Agent):
             raise TypeError("from_module: the output activation is none or Tanh")
         if len(set(acts)) > 1:
             raise TypeError("from_module: mixed hidden activations (one kind per network)")
+        return layers, acts[0] if acts else "tanh", out_act
+
+    @classmethod
+    def from_module(cls, module, **kw):
+        """From an ``nn.Sequential`` of ``Linear`` / ``ReLU`` / ``Tanh`` (SB3's
+        ``mlp_extractor.policy_net`` followed by ``action_net``, flattened into
+        one Sequential): a Linear, then activation and Linear alternating, an
+        optional activation at the end (which must be Tanh).  The parameters are
+        copied as float32.  Anything else, or two different hidden activations,
+        is a TypeError.  Other arguments go to the constructor."""
+        layers, act, out_act = cls._walk(module)
         if "activation" in kw or "out_activation" in kw:
             raise TypeError("from_module reads the activations from the module")
-        return cls(layers, activation=acts[0] if acts else "tanh", out_activation=out_act, **kw)
+        return cls(layers, activation=act, out_activation=out_act, **kw)
 
     def device_spec(self, env):
         raise TypeError("MLPPolicyAgent runs in its own kernel: use rollout_policy / evaluate_agent / env.mlp_actions")
@@ -582,9 +598,14 @@ class MLPPolicyAgent(_Agent):
         hit = self._objs.get(env)
         if hit is not None and hit[0] is env._h:
             return hit[1]
-        if self.dims[0] != env.obs_dim or self.dims[-1] != env.action_dim:
+        if self._updated:
+            raise RuntimeError(f"{self.name}: update_from_module has replaced the parameters on the env it was called "
+                               "with, and this object's host arrays are the old ones: build a new agent from the "
+                               "module for another env")
+        out_dim = 1 if self._value else env.action_dim
+        if self.dims[0] != env.obs_dim or self.dims[-1] != out_dim:
             raise ValueError(f"the network maps {self.dims[0]} -> {self.dims[-1]}, the env needs "
-                             f"{env.obs_dim} -> {env.action_dim}")
+                             f"{env.obs_dim} -> {out_dim}")
         n = len(self.weights)
         ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
         dims = np.asarray(self.dims, np.int32)
@@ -598,10 +619,97 @@ class MLPPolicyAgent(_Agent):
                              ptr(self.in_scale), ptr(self.in_shift), ptr(self.out_scale), ptr(self.out_shift),
                              low.ctypes.data, high.ctypes.data)
         obj = C.c_void_p()
-        _capi.check(env._lib.invsim_mlp_create(env._h, C.byref(spec), C.byref(obj)), env._h, "mlp_create")
+        create = env._lib.invsim_mlp_create_value if self._value else env._lib.invsim_mlp_create
+        _capi.check(create(env._h, C.byref(spec), C.byref(obj)), env._h, "mlp_create")
         env._mlps.append(obj)            # the env destroys it in close(), before its handle
         self._objs[env] = (env._h, obj)
         return obj
+
+    def _module_params(self, module):
+        """The (weight, bias) parameters of ``module``'s Linear layers, checked
+        against this network's ``dims`` (ValueError) before anything else happens."""
+        lin = [m for m in module.modules() if isinstance(m, torch.nn.Linear)]
+        if len(lin) != len(self.dims) - 1:
+            raise ValueError(f"{self.name}: the module has {len(lin)} Linear layers, the network {len(self.dims) - 1}")
+        for l, m in enumerate(lin):
+            if tuple(m.weight.shape) != (self.dims[l + 1], self.dims[l]):
+                raise ValueError(f"{self.name}: layer {l} is {tuple(m.weight.shape)} in the module, "
+                                 f"{(self.dims[l + 1], self.dims[l])} in the network")
+        return [(m.weight, m.bias) for m in lin]
+
+    def update_from_module(self, env, module, log_std=None):
+        """Write ``module``'s current parameters into this network's device copy
+        on ``env``: one small launch on the env's stream (``invsim_mlp_update``),
+        no allocation by the library, no host copy, no synchronisation, legal
+        under ``env.capture`` (a replay re-reads the tensors, so a captured
+        iteration picks up the optimiser's weights).  The module's Linear layers
+        must have this network's shapes (ValueError); float32 contiguous
+        parameters on ``env.device`` are read in place, others are copied there
+        first; a layer without a bias keeps the bias the object has.  A
+        ``GaussianMLPPolicyAgent`` takes ``log_std`` too (``exp`` runs in torch,
+        float32).  The tensors passed stay referenced until the next update.
+        The host arrays of this object are NOT refreshed: afterwards it serves
+        ``env`` only, and meeting another env raises."""
+        params = self._module_params(module)
+        if log_std is not None and (self._value or not hasattr(self, "log_std")):
+            raise TypeError(f"{type(self).__name__} has no Gaussian: log_std goes with a GaussianMLPPolicyAgent")
+        if log_std is not None and tuple(log_std.shape) != (self.dims[-1],):
+            raise ValueError(f"log_std must have shape {(self.dims[-1],)}, got {tuple(log_std.shape)}")
+        obj = self.device_object(env)
+
+        def on_device(t):
+            t = t.detach()
+            if t.dtype == torch.float32 and t.is_contiguous() and t.device == env.device:
+                return t
+            return t.to(device=env.device, dtype=torch.float32).contiguous()
+        ws = [on_device(w) for w, _ in params]
+        bs = [None if b is None else on_device(b) for _, b in params]
+        ls = None if log_std is None else on_device(log_std)
+        sd = None if ls is None else ls.exp()
+        n = len(ws)
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        W = (C.c_void_p * n)(*[p(w) for w in ws])
+        B = (C.c_void_p * n)(*[p(b) for b in bs])
+        _capi.check(env._lib.invsim_mlp_update(env._h, obj, C.cast(W, C.c_void_p), C.cast(B, C.c_void_p), p(sd), p(ls),
+                                               env._stream()), env._h, "mlp_update")
+        self._live = (ws, bs, sd, ls)
+        self._updated = True
+
+
+class ValueMLP(MLPPolicyAgent):
+    """A critic evaluated by the library: the ``MLPPolicyAgent`` network with
+    one output unit and no action conversion, under the same arithmetic
+    contract (``include/invsim.h``, "Critic, GAE and parameter updates").
+    ``env.mlp_values(critic, obs)`` is the launch, over any number of obs rows;
+    ``collect_rollout(..., critic=...)`` evaluates it over the collected rows
+    and feeds ``gae``.  ``out_scale`` / ``out_shift`` ``[1]`` de-normalise the
+    value.  A last width other than 1 is a ValueError."""
+
+    _value = True
+
+    def __init__(self, layers, activation="tanh", in_scale=None, in_shift=None, out_scale=None, out_shift=None,
+                 name="Value"):
+        super().__init__(layers, activation=activation, out_activation=None, in_scale=in_scale, in_shift=in_shift,
+                         out_scale=out_scale, out_shift=out_shift, clip=False, name=name)
+        if self.dims[-1] != 1:
+            raise ValueError(f"a ValueMLP ends in one unit, got {self.dims[-1]}")
+
+    @classmethod
+    def from_module(cls, module, **kw):
+        """``MLPPolicyAgent.from_module`` for a critic: no output activation."""
+        layers, act, out_act = cls._walk(module)
+        if out_act is not None:
+            raise TypeError("ValueMLP.from_module: a critic has no output activation")
+        if "activation" in kw:
+            raise TypeError("from_module reads the activations from the module")
+        return cls(layers, activation=act, **kw)
+
+    def device_spec(self, env):
+        raise TypeError("ValueMLP is a critic: use env.mlp_values / collect_rollout(critic=...)")
+
+    def update_from_module(self, env, module):
+        """``MLPPolicyAgent.update_from_module`` for the critic."""
+        super().update_from_module(env, module)
 
 
 class GaussianMLPPolicyAgent(MLPPolicyAgent):
@@ -699,7 +807,56 @@ def _rollout_mlp_sample(env, agent, K, obs, rewards, actions, metrics, obs0, raw
     return out
 
 
-def collect_rollout(env, agent, K, obs0, metrics=None):
+def gae(reward, terminated, truncated, value0, values, gamma=0.99, gae_lambda=0.95, done0=None, stream=None):
+    """Generalised advantage estimation over K rows of a rollout, one HIP launch
+    (``invsim_gae``; the recurrence is stated op by op in ``include/invsim.h``,
+    "Critic, GAE and parameter updates", float64 inside).  ``reward`` [K, n]
+    float64; ``terminated`` / ``truncated`` [K, n] bool or uint8, either may be
+    ``None``; ``value0`` [n] float32, V of the observation the first step's
+    policy saw; ``values`` [K, n] float32, V of obs row k; ``done0`` [n], the
+    done flag of the row before this block (the previous call's last row), or
+    ``None``.  A truncated step bootstraps from ``gamma * values[k]``, the
+    value of its final observation; the row after a finished episode (NEXT_STEP
+    autoreset's reset row) is no transition: advantage 0, ``valid`` False.
+    Returns a dict of device tensors ``advantages`` / ``returns`` float32 and
+    ``valid`` bool, all [K, n].  ``stream``: a raw stream handle (default:
+    torch's current stream on ``reward``'s device)."""
+    dev = reward.device
+    if reward.dim() != 2:
+        raise ValueError(f"reward must be [K, n], got {tuple(reward.shape)}")
+    K, n = reward.shape
+
+    def flag(t, shape, what):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, device=dev)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+        return (t if t.dtype in (torch.bool, torch.uint8) else t != 0).contiguous()
+
+    def f32(t, shape, what):
+        t = torch.as_tensor(t, device=dev)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+        return t.to(torch.float32).contiguous()
+    reward = reward.to(torch.float64).contiguous()
+    te, tr = flag(terminated, (K, n), "terminated"), flag(truncated, (K, n), "truncated")
+    d0 = flag(done0, (n,), "done0")
+    v0, v = f32(value0, (n,), "value0"), f32(values, (K, n), "values")
+    out = {"advantages": torch.empty((K, n), dtype=torch.float32, device=dev),
+           "returns": torch.empty((K, n), dtype=torch.float32, device=dev),
+           "valid": torch.empty((K, n), dtype=torch.bool, device=dev)}
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(_capi.lib().invsim_gae(p(reward), p(te), p(tr), p(d0), p(v0), p(v), int(K), int(n), float(gamma),
+                                           float(gae_lambda), p(out["advantages"]), p(out["returns"]), p(out["valid"]),
+                                           stream), None, "invsim_gae")
+    return out
+
+
+def collect_rollout(env, agent, K, obs0, metrics=None, critic=None, gamma=0.99, gae_lambda=0.95, done0=None):
     """K steps of every env under a ``GaussianMLPPolicyAgent``, everything an
     on-policy rollout buffer stores, from one C call (two launches per step,
     no Python in the loop).  Returns device tensors: ``obs`` [K, N, O] (row k is
@@ -708,11 +865,42 @@ def collect_rollout(env, agent, K, obs0, metrics=None):
     with), ``raw_actions`` [K, N, A] and ``log_prob`` [K, N] float32 (the
     unclipped sample and its log-density), ``reward`` [K, N] float64,
     ``terminated`` / ``truncated`` [K, N] bool.  ``metrics`` as in
-    ``rollout_policy``.  Values are the caller's: one batched critic call over
-    ``obs``."""
+    ``rollout_policy``.
+
+    With ``critic`` (a ``ValueMLP``, or any callable taking the float32
+    observations ``[K + 1, N, O]`` of ``obs0`` and the K rows) the values and
+    advantages come with it, three more launches and no host synchronisation:
+    ``values`` [K, N] float32, V of each step's input observation,
+    ``last_value`` [N], V of the last row; ``advantages`` / ``returns`` /
+    ``valid`` [K, N] from ``gae`` with ``gamma`` / ``gae_lambda``; ``done`` [N]
+    bool, the last row's terminated | truncated, which is the next call's
+    ``done0`` (``None``: no env finished just before ``obs0``).  Rows with
+    ``valid`` False are NEXT_STEP reset rows: mask them out of the loss.
+    Without a critic the call and its result are what they were."""
     if not isinstance(agent, GaussianMLPPolicyAgent):
         raise TypeError("collect_rollout needs a GaussianMLPPolicyAgent")
-    return _rollout_mlp_sample(env, agent, int(K), True, True, True, metrics, obs0, raw=True, log_prob=True)
+    K = int(K)
+    if critic is None:
+        return _rollout_mlp_sample(env, agent, K, True, True, True, metrics, obs0, raw=True, log_prob=True)
+    if not isinstance(critic, ValueMLP) and not callable(critic):
+        raise TypeError("critic must be a ValueMLP or a callable on the observations")
+    if obs0 is not None:
+        obs0 = torch.as_tensor(obs0, device=env.device).to(env.obs_dtype).contiguous()
+    out = _rollout_mlp_sample(env, agent, K, True, True, True, metrics, obs0, raw=True, log_prob=True)
+    N = env.num_envs
+    if isinstance(critic, ValueMLP):
+        v = torch.empty((K + 1, N), dtype=torch.float32, device=env.device)
+        env._mlp_values_into(critic, obs0, N, v[0])
+        env._mlp_values_into(critic, out["obs"], K * N, v[1:])
+    else:
+        v = critic(torch.cat([obs0[None], out["obs"]]).float())
+        v = v.detach().reshape(K + 1, N).to(torch.float32).contiguous()
+    out.update(gae(out["reward"], out["terminated"], out["truncated"], v[0], v[1:], gamma, gae_lambda, done0,
+                   stream=env._stream()))
+    out["values"], out["last_value"] = v[:K], v[K]
+    out["done"] = (out["terminated"][K - 1] | out["truncated"][K - 1]) if K else torch.zeros(N, dtype=torch.bool,
+                                                                                          device=env.device)
+    return out
 
 
 def _rollout_mlp(env, agent, K, obs, rewards, actions, metrics, obs0):
@@ -757,6 +945,8 @@ def rollout_policy(env, agent, K, obs=False, rewards=True, actions=False, metric
     policy produced at every step, reset steps included)."""
     if isinstance(agent, TorchPolicyAgent):
         return _rollout_torch(env, agent, int(K), obs, rewards, actions, metrics, obs0)
+    if isinstance(agent, ValueMLP):
+        raise TypeError("a ValueMLP is a critic, not a policy: see collect_rollout(critic=...)")
     if isinstance(agent, GaussianMLPPolicyAgent):
         return _rollout_mlp_sample(env, agent, int(K), obs, rewards, actions, metrics, obs0)
     if isinstance(agent, MLPPolicyAgent):

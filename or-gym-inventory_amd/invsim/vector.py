@@ -365,6 +365,23 @@ class InvSimVectorEnv:
                     self._h, "mlp_sample")
         return out
 
+    def _mlp_values_into(self, critic, obs, rows, out):
+        """invsim_mlp_values: `rows` contiguous obs rows (obs dtype) -> the contiguous float32 tensor `out`"""
+        _capi.check(self._lib.invsim_mlp_values(self._h, critic.device_object(self), obs.data_ptr(), int(rows),
+                                                out.data_ptr(), self._stream()), self._h, "mlp_values")
+
+    def mlp_values(self, critic, obs):
+        """One launch of a ValueMLP on obs [..., O] (the env's obs dtype, any
+        number of leading dimensions: a whole [K, N, O] block at once): the
+        values, float32 [...].  Env state is not touched."""
+        o = torch.as_tensor(obs, device=self.device)
+        if o.dim() < 1 or o.shape[-1] != self.obs_dim:
+            raise ValueError(f"obs must have shape [..., {self.obs_dim}], got {tuple(o.shape)}")
+        o = o.to(self.obs_dtype).contiguous()
+        v = self._alloc(*o.shape[:-1], dtype=torch.float32)
+        self._mlp_values_into(critic, o, v.numel(), v)
+        return v
+
     # -- RandomAgent's action stream (include/invsim.h "RandomAgent") ----------
     def _action_high(self):
         """The action space's upper bounds in the action dtype (host array)."""
