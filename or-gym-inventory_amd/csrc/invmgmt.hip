@@ -27,43 +27,22 @@
 #include "kernels.hpp"
 #include "launch.hpp"
 
-// invmgmt_rnd.hip compiles this file with INVSIM_IM_RND_TU: every policy kernel
-// instantiated there is the RANDOM (RandomAgent) variant (kernels.hpp ActGen),
-// whose dynamics code draws each launch step's order from the env's action
-// generator -- before the reset / overrun branches, so every launch step
-// draws -- instead of asking an agent.  Without the macro this file is the
-// text it was: the other translation units' kernels do not change.
-#ifdef INVSIM_IM_RND_TU
-#define IM_RND 1
-#define IM_RND_PARAM , ActGen &ag
-#define IM_RND_ARG , ag
-#else
-#define IM_RND 0
-#define IM_RND_PARAM
-#define IM_RND_ARG
-#endif
-// invmgmt_ext.hip compiles this file with INVSIM_IM_EXT_TU: the policy
-// instantiations of im_run_kernel there are the EXTERNAL variant
-// (invsim_rollout_metrics): the policy bookkeeping (metrics, optional outputs)
-// with the caller's action rows (io.act), read as the open-loop path reads
-// them.  That translation unit defines im_ext_launch and emits im_run_kernel
-// only: the fused rollout kernels have no EXT variant.
-#ifdef INVSIM_IM_EXT_TU
-#define IM_EXT 1
-#else
-#define IM_EXT 0
-#endif
-// invmgmt_lvl.hip compiles this file with INVSIM_IM_LVL_TU: every policy kernel
-// instantiated there is the LEVELS variant, BaseStock's inventory position
-// against the env's own order-up-to levels (and optional reorder points) from
-// the attached device arrays instead of one (L + 1) * mu * sf target.  As for
-// RANDOM the variant is a translation unit, so the other objects' kernels pay
-// neither the per-env loads nor their registers.
-#ifdef INVSIM_IM_LVL_TU
-#define IM_LVL 1
-#else
-#define IM_LVL 0
-#endif
+// The in-kernel policy variants are trailing template arguments of the policy
+// kernels (launch.hpp RunMode), false in every other instantiation:
+//   RND  RANDOM (RandomAgent, kernels.hpp ActGen): the dynamics code draws each
+//        launch step's order from the env's action generator -- before the
+//        reset / overrun branches, so every launch step draws -- instead of
+//        asking an agent.  im_run_kernel and the fused rollouts.
+//   EXT  EXTERNAL (invsim_rollout_metrics): the policy bookkeeping (metrics,
+//        optional outputs) with the caller's action rows (io.act), read as the
+//        open-loop path reads them.  im_run_kernel only: the fused rollout
+//        kernels have no EXT variant.
+//   LVL  LEVELS: BaseStock's inventory position against the env's own
+//        order-up-to levels (and optional reorder points) from the attached
+//        device arrays instead of one (L + 1) * mu * sf target.  im_run_kernel
+//        and the fused rollouts.
+// Which instantiations an object holds is decided where the launchers are
+// defined, at the end of this file.
 
 namespace invsim {
 namespace {
@@ -233,7 +212,6 @@ __device__ __forceinline__ int64_t im_base_stock_order(const PolicyIO &pol, int 
     return (int64_t)x;                                              // astype(int64)
 }
 
-#if IM_LVL
 // INVSIM_POLICY_LEVELS for one stage (invsim.h): order up to the env's level lv
 // over the inventory position pos, only while pos is below the reorder point ro
 // (the strict < of the reference's sSPolicyAgent; +inf without reorder points,
@@ -248,7 +226,8 @@ __device__ __forceinline__ int64_t im_levels_order(double lv, double ro, int64_t
 }
 
 // An env's row of the attached arrays (row: the env, clamped to N - 1 by the
-// caller: the arrays are [N][M1], not padded)
+// caller: the arrays are [N][M1], not padded).  Only a LVL instantiation loads
+// it; elsewhere the unused local costs nothing.
 template <int M1>
 struct ImLevels {
     double lv[M1], ro[M1];
@@ -265,7 +244,6 @@ struct ImLevels {
 // at its 256-VGPR cap (waves_per_eu(2)), would spill 4 VGPRs (20 B of scratch)
 // to hold it, so it reads the row again at the top of every step (cache
 // resident after the first) and is back at 254 VGPRs without scratch.
-#endif
 
 // The PTRS right-hand-side table (or, without one, any valid words) into a
 // TableStage bound for dst in LDS: a fixed count of clamped loads, issued in
@@ -317,6 +295,16 @@ struct ImState {
     uint64_t u32;        // PCG64 32-bit buffer (dist 3 only)
     int64_t I[M1];
     int64_t B[M1 + 1];
+};
+// ... of a RND instantiation of im_run_kernel: with the env's action generator
+// (loaded and stored once per launch, as g) and the launch step's draw.  A
+// type of its own and not locals that the other instantiations leave unused:
+// an unused local, in the kernel or in im_launch_step, changed the code the
+// compiler generates for some of them (register numbers, instruction order).
+template <int M1, bool BACKLOG, class G>
+struct ImStateRnd : ImState<M1, BACKLOG, G> {
+    ActGen ag;
+    int64_t act[M1];
 };
 
 // reset (:197-220): I = I0, B = 0; obs row = [I0, 0...] (lane j of the group
@@ -528,16 +516,14 @@ __device__ __forceinline__ void im_flush_pending(const ImParams &P, const ImPend
 
 // BaseStockAgent.get_action with the inventory position summed from the
 // action_log ring: on hand + the requested orders of the last L_i periods
-// (action_log[max(0, t - L_i) : t, i])
-template <int M1, bool BACKLOG, class G = Pcg>
+// (action_log[max(0, t - L_i) : t, i]).  LVL: against the env's own levels.
+template <int M1, bool BACKLOG, bool LVL, class G>
 __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO &pol, const ImState<M1, BACKLOG, G> &st,
                                               int t, int64_t e, int64_t (&act)[M1]) {
     const int64_t S = P.cm.Npad;
     const int D = P.lt_max;
-#if IM_LVL
     ImLevels<M1> lvl;                                               // (lanes past N: the last env's row)
-    lvl.load(pol, e < P.cm.N ? e : P.cm.N - 1);
-#endif
+    if constexpr (LVL) lvl.load(pol, e < P.cm.N ? e : P.cm.N - 1);
 #pragma unroll
     for (int i = 0; i < M1; i++) {
         const int L = P.L[i];
@@ -551,23 +537,21 @@ __device__ __forceinline__ void im_base_stock(const ImParams &P, const PolicyIO 
             }
             pos = wrap_add(pos, pipe);
         }
-#if IM_LVL
-        act[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
-#else
-        act[i] = im_base_stock_order(pol, L, pos, P.c[i]);
-#endif
+        if constexpr (LVL) act[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+        else act[i] = im_base_stock_order(pol, L, pos, P.c[i]);
     }
 }
 
 // Step k of a launch for the wave's envs: step (or NEXT_STEP reset) into the
 // LDS obs tile, SAME_STEP final-obs/reset, then the tile's coalesced store.
-template <int M1, bool BACKLOG, bool STEP_ONLY, bool POL, bool NPD, class G = Pcg>
+// ST: ImState, or ImStateRnd in a RND instantiation.
+template <int M1, bool BACKLOG, bool STEP_ONLY, bool POL, bool NPD, bool RND, bool EXT, bool LVL, class ST>
 __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<int64_t, int64_t> &io, int k,
                                                int64_t e, int64_t e0, int lane, bool valid, int nvalid,
-                                               ImState<M1, BACKLOG, G> &st, int &t, bool &fault,
+                                               ST &st, int &t, bool &fault,
                                                int64_t *tile, int64_t *trow, const double *rhs,
                                                TableStage *ts, const double *pre_apow, const int64_t *pre_udem,
-                                               const PolicyIO &pol, double *met IM_RND_PARAM) {
+                                               const PolicyIO &pol, double *met) {
     const int j = lane & (LPE - 1);
     const bool leader = j == 0;
     const int64_t N = P.cm.N;
@@ -578,15 +562,14 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
     double rew = 0.0;
     int64_t dem = 0;
     ImPending<M1> pend;
-#if IM_RND
-    int64_t ract[M1];
+    if constexpr (RND) {
 #pragma unroll
-    for (int i = 0; i < M1; i++) ract[i] = act_draw(ag.g, pol.ci[i]);
-    if (valid && leader && pol.act_out) {
+        for (int i = 0; i < M1; i++) st.act[i] = act_draw(st.ag.g, pol.ci[i]);
+        if (valid && leader && pol.act_out) {
 #pragma unroll
-        for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, ract[i]);
+            for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, st.act[i]);
+        }
     }
-#endif
     if (!STEP_ONLY && ts) {   // all lanes write the table before the divergent branch
         ts->flush(lane);
         ts = nullptr;
@@ -615,14 +598,13 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
         const int64_t udem = pre_udem ? *pre_udem : P.user_D[t];
         const int64_t *arow = io.act + ea * M1;
         int64_t pact[M1];
-#if IM_RND
-        arow = ract;
-#elif IM_EXT
-        // the caller's row, as without a policy
-#else
-        if (POL) {
-            if (IM_LVL || pol.kind == POL_BASE_STOCK) {
-                im_base_stock<M1, BACKLOG>(P, pol, st, t, e, pact);
+        if constexpr (RND) {
+            arow = st.act;
+        } else if constexpr (EXT) {
+            // the caller's row, as without a policy
+        } else if (POL) {
+            if (LVL || pol.kind == POL_BASE_STOCK) {
+                im_base_stock<M1, BACKLOG, LVL>(P, pol, st, t, e, pact);
             } else {
 #pragma unroll
                 for (int i = 0; i < M1; i++) pact[i] = pol.ci[i];
@@ -633,7 +615,6 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
             }
             arow = pact;
         }
-#endif
         tr = im_step_regs<M1, BACKLOG, NPD>(P, e, valid, j, t, st, arow, trow, rhs, ts, apow, udem, r, d,
                                             POL ? met : nullptr,
                                             (valid && leader && k == io.K - 1) ? (int64_t *)P.cm.info_rec : nullptr,
@@ -678,7 +659,8 @@ __device__ __forceinline__ void im_launch_step(const ImParams &P, const StepIO<i
     wave_lds_sync();
 }
 
-template <int M1, bool BACKLOG, bool TU, bool ONE, bool POL, bool NPD, class G>
+template <int M1, bool BACKLOG, bool TU, bool ONE, bool POL, bool NPD, class G, bool RND = false, bool EXT = false,
+          bool LVL = false>
 __global__ void __launch_bounds__(WAVE)
 im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     extern __shared__ __attribute__((aligned(16))) int64_t im_tile[];
@@ -730,7 +712,7 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     // state rows are Npad wide, so every lane loads unconditionally (straight-line
     // loads keep the compiler's vmcnt waits exact); lanes past N take the last
     // env's PCG64 stream (an all-zero stream would never leave the PTRS loop)
-    ImState<M1, BACKLOG, G> st;
+    std::conditional_t<RND, ImStateRnd<M1, BACKLOG, G>, ImState<M1, BACKLOG, G>> st;
     P.cm.rng.load(valid ? e : N - 1, st.g);
     st.g.set_step(P.cm.ph_step);
     st.u32 = (NPD && !G::kCounter) ? P.cm.u32buf[valid ? e : N - 1] : 0;
@@ -740,23 +722,21 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     for (int q = 0; q <= M1; q++) st.B[q] = BACKLOG ? P.B[q * S + e] : 0;
     int t = t0;
     bool fault = false;
-#if IM_RND
-    ActGen ag;
-    ag.load(pol, S, valid ? e : N - 1);
-#endif
+    if constexpr (RND) st.ag.load(pol, S, valid ? e : N - 1);
     constexpr int MD = 6;                       // metrics (invsim.h INVSIM_METRICS_*)
     double met[MD];
 #pragma unroll
     for (int q = 0; q < MD; q++) met[q] = (POL && pol.metrics) ? pol.metrics[(valid ? e : N - 1) * MD + q] : 0.0;
     if (ONE) {
-        im_launch_step<M1, BACKLOG, TU, false, NPD>(P, io, 0, e, e0, lane, valid, nvalid, st, t, fault, im_tile, trow,
-                                               rhs_l, &ts, &apow0, &udem0, pol, met IM_RND_ARG);
+        im_launch_step<M1, BACKLOG, TU, false, NPD, RND, EXT, LVL>(P, io, 0, e, e0, lane, valid, nvalid, st, t, fault,
+                                                                   im_tile, trow, rhs_l, &ts, &apow0, &udem0, pol, met);
     } else {
         ts.flush(lane);
         for (int k = 0; k < io.K; k++) {
             st.g.set_step(P.cm.ph_step + (uint64_t)k);
-            im_launch_step<M1, BACKLOG, false, POL, NPD>(P, io, k, e, e0, lane, valid, nvalid, st, t, fault, im_tile,
-                                                    trow, rhs_l, nullptr, nullptr, nullptr, pol, met IM_RND_ARG);
+            im_launch_step<M1, BACKLOG, false, POL, NPD, RND, EXT, LVL>(P, io, k, e, e0, lane, valid, nvalid, st, t, fault,
+                                                                        im_tile, trow, rhs_l, nullptr, nullptr, nullptr,
+                                                                        pol, met);
         }
     }
     if (valid && leader) {
@@ -774,9 +754,7 @@ im_run_kernel(ImParams P, int t_u, StepIO<int64_t, int64_t> io, PolicyIO pol) {
 #pragma unroll
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
-#if IM_RND
-        ag.store(pol, S, e);
-#endif
+        if constexpr (RND) st.ag.store(pol, S, e);
     }
     TWAIT();
     TPROBE(5);
@@ -803,10 +781,6 @@ im_reset_kernel(ImParams P, const uint8_t *__restrict__ mask, int64_t *__restric
     }
 }
 
-// The EXT translation unit (invmgmt_ext.hip) holds im_run_kernel only: the
-// split step, the fused rollouts, the commit kernel and their launchers are
-// left out of it.
-#if !IM_EXT
 // Cross-wave LDS handoff inside a workgroup: orders LDS traffic only (an
 // __syncthreads() would also drain each wave's outstanding global loads and
 // stores, s_waitcnt vmcnt(0), before the s_barrier)
@@ -1427,7 +1401,8 @@ struct ImLt3 {
 // waves_per_eu(2): at most 256 registers in all, so two dynamics waves share a
 // SIMD (the policy variant sits at 256 VGPRs, and the compiler would otherwise
 // take AGPRs beyond them: one wave per SIMD, measured 104 -> 166 us)
-template <int L0, int L1, int L2, bool BACKLOG, bool POL, class RG = Pcg>
+// RND, LVL: the policy variants (the top of this file).
+template <int L0, int L1, int L2, bool BACKLOG, bool POL, class RG = Pcg, bool RND = false, bool LVL = false>
 __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
 im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO pol, int g0) {
     using G = ImLt3<L0, L1, L2>;
@@ -1502,10 +1477,8 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
     double napow = P.alpha_pow[t < P.periods ? t : 0];   // alpha**t of the next step, prefetched
     int64_t dlast = 0;
     bool last_real = false;
-#if IM_RND
     ActGen ag;
-    ag.load(pol, S, el);
-#endif
+    if constexpr (RND) ag.load(pol, S, el);
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
     // the group's partials are read only after the loop (they would hold 8
     // VGPRs through it: the policy kernel then needs AGPRs, one wave per SIMD)
@@ -1522,23 +1495,21 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
             int64_t req[M1];
 #pragma unroll
             for (int i = 0; i < M1; i++) req[i] = nact[i];
-#if IM_RND
+            if constexpr (RND) {
 #pragma unroll
-            for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
-            if (valid && pol.act_out) {
+                for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
+                if (valid && pol.act_out) {
 #pragma unroll
-                for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+                    for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+                }
             }
-#endif
             const double apow = napow;
             {
                 const int tn = (t >= P.periods) ? 0 : t + 1;     // the next launch step's period
                 napow = P.alpha_pow[tn < P.periods ? tn : 0];
             }
-#if IM_LVL
-            ImLevels<M1> lvl;                      // read again every step (see ImLevels)
-            lvl.load(pol, el);
-#endif
+            ImLevels<M1> lvl;                      // LVL: read again every step (see ImLevels)
+            if constexpr (LVL) lvl.load(pol, el);
             if (!POL && k + 1 < K) {               // prefetch the next step's actions
 #pragma unroll
                 for (int i = 0; i < M1; i++) nact[i] = io.act[((int64_t)(k + 1) * N + el) * M1 + i];
@@ -1559,8 +1530,8 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                 t = 0;
             } else {
                 const int64_t d = db[kk * WAVE + lane];
-                if (POL && !IM_RND) {
-                    if (IM_LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register windows
+                if (POL && !RND) {
+                    if (LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register windows
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
                             constexpr int DD = D;
@@ -1572,11 +1543,8 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
                                 if (t - a >= 0) pipe = wrap_add(pipe, v);
                             }
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
-#if IM_LVL
-                            req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
-#else
-                            req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
-#endif
+                            if constexpr (LVL) req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+                            else req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
                         }
                     } else {
 #pragma unroll
@@ -1692,9 +1660,7 @@ im_roll3_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO p
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
         if (ep_part) P.cm.ep_ret[e] = ep.r;
-#if IM_RND
-        if (POL) ag.store(pol, S, e);
-#endif
+        if constexpr (RND) ag.store(pol, S, e);
     }
     if (ep_part) {
         EpPart epp;
@@ -1757,7 +1723,8 @@ struct ImLt3o : ImLt3<L0, L1, L2> {
 // one SIMD and waves 2 and 3 on a SIMD each (tools/wave_placement,
 // profiles/r03/launch/placement.txt), so the two dynamics waves take waves 2
 // and 3 and every demand wave shares its SIMD with the other group's obs wave.
-template <int L0, int L1, int L2, bool BACKLOG, bool POL, class RG = Pcg, int G2 = 1>
+// RND, LVL: the policy variants (the top of this file), in the dynamics wave.
+template <int L0, int L1, int L2, bool BACKLOG, bool POL, class RG = Pcg, int G2 = 1, bool RND = false, bool LVL = false>
 __global__ void __launch_bounds__(3 * WAVE * G2)
 im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO pol) {
     using G = ImLt3o<L0, L1, L2>;
@@ -1921,14 +1888,10 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     for (int i = 0; i < M1; i++) nact[i] = POL ? 0 : io.act[el * M1 + i];
     int64_t dlast = 0;
     bool last_real = false;
-#if IM_RND
     ActGen ag;
-    ag.load(pol, S, el);
-#endif
-#if IM_LVL
-    ImLevels<M1> lvl;                              // held over the K steps
-    lvl.load(pol, el);
-#endif
+    if constexpr (RND) ag.load(pol, S, el);
+    ImLevels<M1> lvl;                              // LVL: held over the K steps (see ImLevels)
+    if constexpr (LVL) lvl.load(pol, el);
     // episode sink (kernels.hpp EpSink), accumulated in registers over the launch;
     // the group's partials are read only after the loop (they would hold 8
     // VGPRs through it: the policy kernel then needs AGPRs, one wave per SIMD)
@@ -1947,14 +1910,14 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
             int64_t req[M1];
 #pragma unroll
             for (int i = 0; i < M1; i++) req[i] = nact[i];
-#if IM_RND
+            if constexpr (RND) {
 #pragma unroll
-            for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
-            if (valid && pol.act_out) {
+                for (int i = 0; i < M1; i++) req[i] = act_draw(ag.g, pol.ci[i]);
+                if (valid && pol.act_out) {
 #pragma unroll
-                for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+                    for (int i = 0; i < M1; i++) out_store((int64_t *)pol.act_out + oi * M1 + i, req[i]);
+                }
             }
-#endif
             if (!POL && k + 1 < K) {    // prefetch the next step's actions
 #pragma unroll
                 for (int i = 0; i < M1; i++) nact[i] = io.act[((int64_t)(k + 1) * N + el) * M1 + i];
@@ -1976,8 +1939,8 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                 t = 0;
             } else {
                 const int64_t d = db[kk * WAVE + lane];
-                if (POL && !IM_RND) {
-                    if (IM_LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register history
+                if (POL && !RND) {
+                    if (LVL || pol.kind == POL_BASE_STOCK) {   // im_base_stock from the register history
 #pragma unroll
                         for (int i = 0; i < M1; i++) {
                             int64_t pos = I[i];                                 // observation[:M1] = I[t]
@@ -1986,11 +1949,8 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
                             for (int a = 0; a < G::lt(i); a++)                  // action_log[max(0, t - L_i) : t, i]
                                 if (t - 1 - a >= 0) pipe = wrap_add(pipe, hv[i][a]);
                             if (G::lt(i) > 0) pos = wrap_add(pos, pipe);
-#if IM_LVL
-                            req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
-#else
-                            req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
-#endif
+                            if constexpr (LVL) req[i] = im_levels_order(lvl.lv[i], lvl.ro[i], pos, P.c[i]);
+                            else req[i] = im_base_stock_order(pol, G::lt(i), pos, P.c[i]);
                         }
                     } else {
 #pragma unroll
@@ -2076,9 +2036,7 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
             for (int q = 0; q < MD; q++) pol.metrics[e * MD + q] = met[q];
         }
         if (ep_part) P.cm.ep_ret[e] = ep.r;
-#if IM_RND
-        if (POL) ag.store(pol, S, e);
-#endif
+        if constexpr (RND) ag.store(pol, S, e);
     }
     if (ep_part) {
         EpPart epp;
@@ -2089,19 +2047,6 @@ im_roll3o_kernel(ImParams P, int t_start, StepIO<int64_t, int64_t> io, PolicyIO 
     TPROBE_W(6);
 }
 
-// cm.rng <- the committed slot of the lookahead cache (see im_split_kernel)
-__global__ void __launch_bounds__(256) im_commit_kernel(ImParams P, int slot) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= P.cm.N) return;
-    const int64_t S = P.cm.Npad;
-    const uint64_t *A = P.ahead + (int64_t)slot * 4 * S;
-    P.cm.rng.hi[e] = A[e];
-    P.cm.rng.lo[e] = A[S + e];
-    if (P.cm.u32buf) P.cm.u32buf[e] = A[3 * S + e];
-}
-#endif  // !IM_EXT
-
-#if !IM_EXT
 // the lock-step split step kernel applies (both streams)
 inline bool im_split_applies(const ImParams &p, int t_u, const PolicyIO *pol, const StepIO<int64_t, int64_t> &io) {
     return !pol && io.K == 1 && t_u >= 0 && t_u < p.periods && io.obs &&
@@ -2127,7 +2072,9 @@ inline bool im_roll_applies(const ImParams &p, int M1, int t_u, const PolicyIO *
            p.cm.kn.im_roll;
 }
 
-template <class RG>
+// Modes: the Run modes whose instantiations the calling unit holds (the end of
+// this file)
+template <class RG, class Modes>
 hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const PolicyIO *pol,
                           const StepIO<int64_t, int64_t> &io, hipStream_t s) {
     const PolicyIO &pv = pol_or_none(pol);
@@ -2152,25 +2099,25 @@ hipError_t im_roll_launch(const ImParams &p, bool backlog, int t_u, const Policy
     // 1 048 576 envs 2 433 -> 2 300 us; sub-launches of 131 072 envs (two
     // rounds each) are slower than one launch, of 16 384 far slower
     const int sub = p.cm.kn.im_roll_sub >= WAVE ? (int)std::min<int64_t>(p.cm.kn.im_roll_sub / WAVE, g3.x) : (int)g3.x;
-    auto launch = [&](auto B_, auto POL_) {
-        constexpr bool B = decltype(B_)::value, POL = decltype(POL_)::value;
+    auto launch = [&](auto B_, auto R_) {
+        constexpr bool B = decltype(B_)::value;
+        using MD = RunMode<decltype(R_)::value>;
+        constexpr bool POL = MD::POL, RND = MD::RND, LVL = MD::LVL;
         if (two)
-            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG, 2>), dim3(g3.x / 2), dim3(6 * WAVE), 2 * G3::lds(POL), s, p,
-                               t_u, io, pv);
+            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG, 2, RND, LVL>), dim3(g3.x / 2), dim3(6 * WAVE),
+                               2 * G3::lds(POL), s, p, t_u, io, pv);
         else if (three)
-            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG>), g3, dim3(3 * WAVE), G3::lds(POL), s, p, t_u, io, pv);
+            hipLaunchKernelGGL((im_roll3o_kernel<1, 5, 10, B, POL, RG, 1, RND, LVL>), g3, dim3(3 * WAVE), G3::lds(POL), s, p,
+                               t_u, io, pv);
         else
             for (int g0 = 0; g0 < (int)g3.x; g0 += sub)
-                hipLaunchKernelGGL((im_roll3_kernel<1, 5, 10, B, POL, RG>), dim3(min(sub, (int)g3.x - g0)), dim3(2 * WAVE),
-                                   G::lds(), s, p, t_u, io, pv, g0);
+                hipLaunchKernelGGL((im_roll3_kernel<1, 5, 10, B, POL, RG, RND, LVL>), dim3(min(sub, (int)g3.x - g0)),
+                                   dim3(2 * WAVE), G::lds(), s, p, t_u, io, pv, g0);
         return hipGetLastError();
     };
+    const Run mode = run_mode_variant(pol, io.K, POL_LEVELS);
     return dispatch_bool(backlog, [&](auto B) {
-#if IM_RND || IM_LVL
-        return launch(B, std::true_type{});   // these translation units hold the policy kernels only
-#else
-        return dispatch_bool(pol != nullptr, [&](auto POL) { return launch(B, POL); });
-#endif
+        return dispatch(Modes{}, mode, [&](auto R) { return launch(B, R); }, invalid_value);
     });
 }
 
@@ -2207,7 +2154,6 @@ inline ImSplitArgs im_split_args(const ImParams &q, const double *ap_host, int M
     }
     return a;
 }
-#endif  // !IM_EXT
 
 // Stage count (M1 stages and the market) and backlog mode -> template arguments:
 // f(Const<M1>, std::bool_constant<backlog>)
@@ -2219,21 +2165,17 @@ hipError_t im_dispatch_shape(int M1, bool backlog, F &&f) {
     }, invalid_value);
 }
 
-// The one-wave run kernel, in every translation unit: the modes this one holds
-// (the RND, LVL and EXT units: the policy instantiation, their variant of it)
-#if IM_RND || IM_LVL || IM_EXT
-using ImRunModes = Values<Run::POLICY>;
-#else
-using ImRunModes = Values<Run::STEP, Run::STEPS, Run::POLICY>;
-#endif
-template <class RG>
+// The one-wave run kernel, in every translation unit.  Modes: the Run modes
+// whose instantiations the calling unit holds (the end of this file); a launch
+// of any other mode is refused.
+template <class RG, class Modes>
 hipError_t im_run_kernel_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO *pol,
                                 const StepIO<int64_t, int64_t> &io, hipStream_t s) {
     const size_t lds = im_run_lds_bytes(M1, p.lt_max);
     const dim3 grid(grid_for(p.cm.N, EPW)), block(WAVE);
     const PolicyIO &pv = pol_or_none(pol);
     const bool npd = p.dist >= 2 && p.dist <= 4;
-    const Run mode = run_mode(pol, io.K);
+    const Run mode = run_mode_variant(pol, io.K, POL_LEVELS);
     return im_dispatch_shape(M1, backlog, [&](auto M_, auto B_) {
         constexpr int M = decltype(M_)::value;
         constexpr bool B = decltype(B_)::value;
@@ -2241,9 +2183,10 @@ hipError_t im_run_kernel_launch(const ImParams &p, int M1, bool backlog, int t_u
             constexpr bool TU = decltype(TU_)::value;
             return dispatch_bool(npd, [&](auto NPD_) {
                 constexpr bool NPD = decltype(NPD_)::value;
-                return dispatch(ImRunModes{}, mode, [&](auto R) {
+                return dispatch(Modes{}, mode, [&](auto R) {
                     using MD = RunMode<decltype(R)::value>;
-                    hipLaunchKernelGGL((im_run_kernel<M, B, TU, MD::ONE, MD::POL, NPD, RG>), grid, block, lds, s, p, t_u, io, pv);
+                    hipLaunchKernelGGL((im_run_kernel<M, B, TU, MD::ONE, MD::POL, NPD, RG, MD::RND, MD::EXT, MD::LVL>), grid,
+                                       block, lds, s, p, t_u, io, pv);
                     return hipGetLastError();
                 }, invalid_value);
             });
@@ -2251,7 +2194,6 @@ hipError_t im_run_kernel_launch(const ImParams &p, int M1, bool backlog, int t_u
     });
 }
 
-#if !IM_EXT
 // im_split_kernel's instantiations: AHEAD = the cache holds this step's demand
 // (else it is drawn inline), EARLY only for a lookahead step
 enum class ImSplit { MISS, HIT, HIT_EARLY };
@@ -2331,52 +2273,61 @@ hipError_t im_launch_rg(const ImParams &p, const double *ap_host, int M1, bool b
     // the in-kernel BaseStock / ConstantOrder agents
     if (im_roll_applies(p, M1, t_u, pol, io)) {
         sunk = true;                  // so do the rollout kernels
-        return im_roll_launch<RG>(p, backlog, t_u, pol, io, s);
+        return im_roll_launch<RG, Values<Run::STEPS, Run::POLICY>>(p, backlog, t_u, pol, io, s);
     }
-    return im_run_kernel_launch<RG>(p, M1, backlog, t_u, pol, io, s);
+    return im_run_kernel_launch<RG, Values<Run::STEP, Run::STEPS, Run::POLICY>>(p, M1, backlog, t_u, pol, io, s);
 }
-#endif  // !IM_EXT
+
+// A variant unit's launch (R = Run::RANDOM or Run::LEVELS), both demand
+// streams: the variant's instantiations of im_roll3o_kernel / im_roll3_kernel
+// where im_roll_applies (the rows of BaseStock / ConstantOrder), of
+// im_run_kernel otherwise.
+template <Run R>
+hipError_t im_variant_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                             const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
+    return dispatch_bool(philox, [&](auto PH) {
+        using RG = std::conditional_t<decltype(PH)::value, PhiloxGen, Pcg>;
+        if (im_roll_applies(p, M1, t_u, &pol, io)) {
+            sunk = true;
+            return im_roll_launch<RG, Values<R>>(p, backlog, t_u, &pol, io, s);
+        }
+        return im_run_kernel_launch<RG, Values<R>>(p, M1, backlog, t_u, &pol, io, s);
+    });
+}
 
 }  // namespace
 
-#if IM_EXT
-// invmgmt_ext.hip: this file compiled a fourth time, for the EXTERNAL variant
-// of im_run_kernel's policy instantiations of both demand streams (one step or
-// K: invsim_rollout_metrics has no fused rollout).  The caller (im_launch_rg)
-// has committed the lookahead cache; the kernel does not fold into the episode
-// sink, so the host folds the output rows.
-hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
-                         const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s) {
-    if (philox) return im_run_kernel_launch<PhiloxGen>(p, M1, backlog, t_u, &pol, io, s);
-    return im_run_kernel_launch<Pcg>(p, M1, backlog, t_u, &pol, io, s);
-}
-#elif IM_RND || IM_LVL
-// invmgmt_rnd.hip / invmgmt_lvl.hip: this file compiled again, for the RANDOM /
-// LEVELS variants of the policy kernels of both demand streams: im_roll3o_kernel
-// / im_roll3_kernel where im_roll_applies (the rows of BaseStock /
-// ConstantOrder), im_run_kernel otherwise.
-template <class RG>
-static hipError_t im_var_launch_rg(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
-                                   const StepIO<int64_t, int64_t> &io, bool &sunk, hipStream_t s) {
-    if (im_roll_applies(p, M1, t_u, &pol, io)) {
-        sunk = true;
-        return im_roll_launch<RG>(p, backlog, t_u, &pol, io, s);
-    }
-    return im_run_kernel_launch<RG>(p, M1, backlog, t_u, &pol, io, s);
-}
-#if IM_LVL
-hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
-                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
-#else
+// The translation units.  This file is compiled five times (invmgmt.hip and
+// the four files that include it under a macro) into five objects, and the
+// macro decides one thing: which exported launchers the object defines.  A
+// launcher names the demand stream and the Run modes it dispatches over, and an
+// object holds the kernel instantiations its launchers name and no other:
+//   invmgmt.o      numpy's PCG64 stream: STEP, STEPS, POLICY; reset and commit
+//   invmgmt_ph.o   the fast stream: STEP, STEPS, POLICY
+//   invmgmt_rnd.o  RANDOM, invmgmt_lvl.o LEVELS, invmgmt_ext.o EXTERNAL: both streams
+// The variants stay out of the first two objects: with the RANDOM kernels in
+// invmgmt.o the lock-step step ran 1.0-1.5 % slower, its own code unchanged
+// (DESIGN, RandomAgent); and the objects compile in parallel.
+#if defined(INVSIM_IM_RND_TU)
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
-#endif
-    if (philox) return im_var_launch_rg<PhiloxGen>(p, M1, backlog, t_u, pol, io, sunk, s);
-    return im_var_launch_rg<Pcg>(p, M1, backlog, t_u, pol, io, sunk, s);
+    return im_variant_launch<Run::RANDOM>(p, M1, backlog, t_u, pol, io, philox, sunk, s);
+}
+#elif defined(INVSIM_IM_LVL_TU)
+hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s) {
+    return im_variant_launch<Run::LEVELS>(p, M1, backlog, t_u, pol, io, philox, sunk, s);
+}
+#elif defined(INVSIM_IM_EXT_TU)
+// im_run_kernel only, one step or K: invsim_rollout_metrics has no fused
+// rollout.  The caller (im_launch_rg) has committed the lookahead cache; the
+// kernel does not fold into the episode sink, so the host folds the output rows.
+hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
+                         const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s) {
+    if (philox) return im_run_kernel_launch<PhiloxGen, Values<Run::EXTERNAL>>(p, M1, backlog, t_u, &pol, io, s);
+    return im_run_kernel_launch<Pcg, Values<Run::EXTERNAL>>(p, M1, backlog, t_u, &pol, io, s);
 }
 #elif defined(INVSIM_IM_FAST_TU)
-// invmgmt_ph.hip: this file compiled a second time for the fast-stream
-// kernels (a TU of their own, so the two instantiation sets compile in parallel)
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s) {
     return im_launch_rg<PhiloxGen>(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);
@@ -2389,6 +2340,19 @@ hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool 
     if (p.cm.philox) return im_run_launch_ph(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);   // invmgmt_ph.hip
     return im_launch_rg<Pcg>(p, ap_host, M1, backlog, t_u, pol, io, la, sunk, s);
 }
+
+namespace {
+// cm.rng <- the committed slot of the lookahead cache (see im_split_kernel)
+__global__ void __launch_bounds__(256) im_commit_kernel(ImParams P, int slot) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P.cm.N) return;
+    const int64_t S = P.cm.Npad;
+    const uint64_t *A = P.ahead + (int64_t)slot * 4 * S;
+    P.cm.rng.hi[e] = A[e];
+    P.cm.rng.lo[e] = A[S + e];
+    if (P.cm.u32buf) P.cm.u32buf[e] = A[3 * S + e];
+}
+}  // namespace
 
 hipError_t im_commit_launch(const ImParams &p, int slot, hipStream_t s) {
     if (p.cm.N == 0 || !p.ahead) return hipSuccess;
@@ -2407,11 +2371,8 @@ hipError_t im_reset_launch(const ImParams &p, int M1, bool backlog, const uint8_
 }
 
 INVSIM_PTRS_STATS_TU(im)
-#endif  // INVSIM_IM_FAST_TU
 
-}  // namespace invsim
-
-#if defined(INVSIM_TIMING) && !defined(INVSIM_IM_FAST_TU) && !IM_RND && !IM_EXT && !IM_LVL
+#ifdef INVSIM_TIMING   // the profiling build's probe buffers (this object's only)
 extern "C" int invsim_debug_timing(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbuf), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }
@@ -2422,3 +2383,6 @@ extern "C" int invsim_debug_timing_bar(void *dst, int64_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(invsim::g_tbar), (size_t)bytes, 0, hipMemcpyDeviceToHost);
 }
 #endif
+#endif
+
+}  // namespace invsim

@@ -1,10 +1,10 @@
 // The EXTERNAL InvMgmt run kernels (invsim_rollout_metrics): invmgmt.hip
-// compiled again with INVSIM_IM_EXT_TU, where im_run_kernel's policy
-// instantiations keep the policy bookkeeping (metrics, optional outputs) but
-// take each step's orders from the caller's action rows, and which defines
-// im_ext_launch.  As for invmgmt_rnd.hip the variant is a macro and not a
-// template argument, so invmgmt.o, invmgmt_ph.o and invmgmt_rnd.o hold the
-// kernels they held before.  Only im_run_kernel is emitted here: the split
-// step and the fused rollout kernels are guarded out of this translation unit.
+// compiled again with INVSIM_IM_EXT_TU, which selects im_ext_launch as the
+// launcher this object defines, and with it the EXT instantiations of
+// im_run_kernel of both demand streams: the policy bookkeeping (metrics,
+// optional outputs) with each step's orders from the caller's action rows.
+// An object of its own, as invmgmt_rnd.hip.  Only im_run_kernel is emitted
+// here: the launcher names no other kernel, and a template that is not
+// instantiated emits nothing.
 #define INVSIM_IM_EXT_TU
 #include "invmgmt.hip"

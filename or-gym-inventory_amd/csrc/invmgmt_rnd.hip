@@ -1,9 +1,9 @@
 // The RANDOM (RandomAgent) InvMgmt policy kernels: invmgmt.hip compiled again
-// with INVSIM_IM_RND_TU, where every policy kernel is the variant that draws
-// its orders from the env's action generator (im_run_kernel, im_roll3o_kernel,
-// im_roll3_kernel, both demand streams), and which defines im_rnd_launch.  The
-// variant is this macro and not a template argument so that invmgmt.hip
-// without it is unchanged text: invmgmt.o and invmgmt_ph.o then hold the
-// kernels they held before RANDOM existed.
+// with INVSIM_IM_RND_TU, which selects im_rnd_launch as the launcher this
+// object defines, and with it the RND instantiations of im_run_kernel,
+// im_roll3o_kernel and im_roll3_kernel of both demand streams (the variant is
+// a template argument; see the end of invmgmt.hip).  An object of its own, so
+// that invmgmt.o and invmgmt_ph.o hold the kernels they held before RANDOM
+// existed.
 #define INVSIM_IM_RND_TU
 #include "invmgmt.hip"

@@ -395,8 +395,8 @@ struct StepIO {
 // POL_EXTERNAL (invsim_rollout_metrics) is internal, not an INVSIM_POLICY_* kind:
 // the policy bookkeeping with the caller's action rows (StepIO::act).  It is a
 // compile-time variant, EXT, of the run kernels only (a trailing template
-// argument; for InvMgmt the translation unit invmgmt_ext.hip, INVSIM_IM_EXT_TU),
-// so no existing instantiation gains a branch.
+// argument; InvMgmt's EXT instantiations are held by an object of their own,
+// invmgmt_ext.hip), so no existing instantiation gains a branch.
 enum { POL_NONE = 0, POL_CONSTANT = 1, POL_BASE_STOCK = 2, POL_ORDER_UP_TO = 3, POL_CLASSIC_NV = 4,
        POL_SS = 5, POL_RANDOM = 6, POL_EXTERNAL = 7, POL_LEVELS = 8, POL_NET_LEVELS = 9 };
 constexpr int POL_MAX_A = 32;
@@ -422,9 +422,9 @@ struct PolicyIO {
 static_assert(sizeof(PolicyIO) == 32 + POL_MAX_A * 12 + 16, "a by-value argument of every policy kernel");
 
 // RANDOM (RandomAgent) is a compile-time variant, RND, of the run kernels and of
-// the fused rollout kernels (their dynamics waves draw); for InvMgmt the variant
-// is a translation unit, invmgmt_rnd.hip (INVSIM_IM_RND_TU), not a template
-// argument, so invmgmt.o's kernels are the text they were: the
+// the fused rollout kernels (their dynamics waves draw), a trailing template
+// argument; InvMgmt's RND instantiations are held by an object of their own,
+// invmgmt_rnd.hip, so invmgmt.o's kernels are the code they were: the
 // action generator's four registers stay live across a launch's K steps, and
 // the other agents' instantiations (RND = false) must not pay for them.  A RND
 // kernel loads the env's action generator once, draws action_dim doubles every
@@ -744,14 +744,14 @@ hipError_t im_run_launch(const ImParams &p, const double *ap_host, int M1, bool 
 // the fast-stream (cm.philox) kernels, invmgmt_ph.hip
 hipError_t im_run_launch_ph(const ImParams &p, const double *ap_host, int M1, bool backlog, int t_u, const PolicyIO *pol,
                             const StepIO<int64_t, int64_t> &io, Lookahead &la, bool &sunk, hipStream_t s);
-// the RANDOM (RND) instantiations of im_run_kernel, invmgmt_rnd.hip (both demand streams)
-// (the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
+// the RANDOM (RND) instantiations of the policy kernels, which invmgmt_rnd.hip's object holds (both
+// demand streams: the fused rollout kernels where im_roll_applies, im_run_kernel otherwise; sunk as im_run_launch's)
 hipError_t im_rnd_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
-// the LEVELS instantiations of the same kernels, invmgmt_lvl.hip (pol.levels / pol.reorder: [N][M1])
+// the LEVELS (LVL) instantiations of the same kernels, invmgmt_lvl.hip's object (pol.levels / pol.reorder: [N][M1])
 hipError_t im_lvl_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, bool &sunk, hipStream_t s);
-// the EXTERNAL instantiations of im_run_kernel, invmgmt_ext.hip (both demand streams):
+// the EXTERNAL (EXT) instantiations of im_run_kernel, invmgmt_ext.hip's object (both demand streams):
 // K >= 1 steps with the actions of io.act and the bookkeeping of pol (the rows are not sunk)
 hipError_t im_ext_launch(const ImParams &p, int M1, bool backlog, int t_u, const PolicyIO &pol,
                          const StepIO<int64_t, int64_t> &io, bool philox, hipStream_t s);

@@ -37,9 +37,10 @@ struct RunMode {
     static constexpr bool RND = R == Run::RANDOM, EXT = R == Run::EXTERNAL, LVL = R == Run::LEVELS;
 };
 inline Run run_mode(const PolicyIO *pol, int K) { return pol ? Run::POLICY : K == 1 ? Run::STEP : Run::STEPS; }
-// ... where the policy variants are template arguments (Newsvendor, NetInvMgmt;
-// InvMgmt's are translation units).  levels_kind: the family's per-env levels
-// policy, or POL_NONE when it has none.
+// ... with the policy variants, which are template arguments in every family
+// (InvMgmt's variant instantiations are held by objects of their own, each of
+// which dispatches over its own mode alone: the end of invmgmt.hip).
+// levels_kind: the family's per-env levels policy, or POL_NONE when it has none.
 inline Run run_mode_variant(const PolicyIO *pol, int K, int levels_kind) {
     if (pol && pol->kind == POL_RANDOM) return Run::RANDOM;
     if (pol && pol->kind == POL_EXTERNAL) return Run::EXTERNAL;

@@ -10,9 +10,14 @@ lookahead transition that occurs with it, and a count and hash of every line
 of the full product (`launch_cases <family> --full` prints them) -- must equal
 tests/golden/launch_choice_{nv,im,net}.txt line for line.  The goldens were
 recorded from the launchers as they were before the launch choice was restated
-(profiles/launch_paths/table.md).
+(profiles/launch_paths/table.md); the InvMgmt one was recorded again when its
+policy variants became template arguments, after its full product, with those
+arguments deleted from the kernel names, had equalled the earlier one byte for
+byte (profiles/im_variants/resources.md).
 """
+import collections
 import os
+import re
 import shutil
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -60,3 +65,36 @@ def test_launch_choice(harness, family):
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, f"line {i + 1} differs"
     assert len(got) == len(want)
+
+
+# a launch record of an InvMgmt run or fused rollout kernel: name, template arguments, arguments
+IM_POLICY_LAUNCH = re.compile(r" \| (im_run_kernel|im_roll3o?_kernel)<([^<>]*)> g=\d+ b=\d+ lds=\d+ \(([^()]*)\)")
+# the trailing template arguments that name the policy variant (csrc/invmgmt.hip)
+IM_VARIANT_ARGS = {"im_run_kernel": ("RND", "EXT", "LVL"), "im_roll3_kernel": ("RND", "LVL"),
+                   "im_roll3o_kernel": ("RND", "LVL")}
+# kernels.hpp POL_RANDOM, POL_EXTERNAL, POL_LEVELS; every other kind, and no policy (0): no variant
+IM_VARIANT_OF_KIND = {6: "RND", 7: "EXT", 8: "LVL"}
+
+
+def test_im_policy_variant_routing(harness):
+    """Every InvMgmt run / rollout launch of the full product goes to the
+    instantiation of its policy's variant: RANDOM to RND, EXTERNAL to EXT,
+    LEVELS to LVL, every other kind and no policy to the one with none of the
+    three.  The golden alone cannot say this: it names the instantiations that
+    occur, not the policy each was launched for."""
+    r = subprocess.run([harness, "im", "--full"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = collections.Counter()
+    for line in r.stdout.splitlines():
+        for name, targs, args in IM_POLICY_LAUNCH.findall(line):
+            names = IM_VARIANT_ARGS[name]
+            on = {n for n, v in zip(names, targs.split(", ")[-len(names):]) if v == "true"}
+            kinds = [int(a[3:]) for a in args.split(",") if a.startswith("pol")]
+            assert len(kinds) == 1, line
+            want = IM_VARIANT_OF_KIND.get(kinds[0])
+            assert on == ({want} if want else set()), line
+            seen[(name, want)] += 1
+    # the product reaches every instantiation family the rule speaks of
+    for name, names in IM_VARIANT_ARGS.items():
+        for want in (None,) + names:
+            assert seen[(name, want)] > 0, (name, want)
