@@ -514,6 +514,94 @@ int invsim_mlp_update(invsim_handle *h, invsim_mlp *m,
                       const float *const *bias /* likewise, [dims[l+1]] */, const float *std,
                       const float *log_std /* DEVICE [A], both or neither */, void *stream);
 
+/* ---- Running normalisation: what SB3's VecNormalize keeps around a PPO / A2C
+ * learner on these envs (observations are raw inventory counts, rewards are in
+ * the hundreds): running moments of the observations, the running variance of
+ * the discounted return, rewards scaled by it, and the network's in_scale /
+ * in_shift rows rewritten from the moments, all on the stream.
+ *
+ * Shared rules.  The entry points without a handle run on the current device,
+ * like invsim_gae; invsim_mlp_set_input_norm runs on its handle's device.  None
+ * allocates or synchronises, all are legal inside a capture bracket, none uses
+ * atomics (the results are deterministic), and every refusal happens on the
+ * host before any launch.  All arithmetic is f64 with one rounding per
+ * operation (no fused multiply-add); division and square root are the IEEE
+ * correctly rounded ones, so a numpy restatement gives the same bits.  NaN and
+ * infinity propagate by the formulas.
+ *
+ * invsim_moments folds the rows of x [rows][cols] (row-major, `dtype` one of
+ * INVSIM_DTYPE_*) into stats, device f64 [3][cols], in/out: row 0 the count,
+ * row 1 the mean, row 2 M2, the sum of squared deviations.  mask [rows] u8 or
+ * NULL: a row counts where its byte is non-zero (NULL: every row).
+ *   leaves  rows are cut into blocks of INVSIM_MOMENTS_BLOCK consecutive rows
+ *           (the last may be short).  Per block and column c:
+ *             n = the number of unmasked rows, as a double
+ *             s = +0.0;  for unmasked r ascending: s = s + (double)x[r][c]
+ *             mean = s / n
+ *             q = +0.0;  for unmasked r ascending: d = (double)x[r][c] - mean;  q = q + d * d
+ *           the leaf is (n, mean, q); a block with no unmasked row is (0, +0.0, +0.0).
+ *   merge   Merge(a, b): if n_b == 0 the result is a; else if n_a == 0 it is b; else
+ *             n = n_a + n_b;  d = mean_b - mean_a;  w = n_b / n
+ *             mean = mean_a + d * w;  M2 = (M2_a + M2_b) + (d * d) * (n_a * w)
+ *   tree    level 0 is the leaves in block order; node i of level l + 1 is
+ *           Merge(node 2i, node 2i + 1) of level l, an unpaired last node passes
+ *           up unchanged; this repeats until one node is left, the batch.  Then
+ *           stats = Merge(stats, batch), the running statistics on the left.
+ * How blocks map to lanes, workgroups and launches is not part of the contract
+ * (any aligned power-of-two group of nodes reduced in one place reproduces the
+ * tree).  scratch is device memory of at least invsim_moments_scratch_bytes
+ * bytes, 8-byte aligned; the call may overwrite all of it.  rows < 0, cols < 1
+ * or an unknown dtype is INVSIM_EINVAL, cols > 1024 INVSIM_ERANGE; then rows == 0
+ * returns INVSIM_OK without a launch; then a NULL x / stats / scratch is
+ * INVSIM_EINVAL and a scratch_bytes below the requirement INVSIM_ERANGE.
+ *
+ * invsim_discounted_returns is VecNormalize's `returns` over K rows.  ret [n]
+ * f64, in/out, is the running discounted return; out [K][n] f64; valid [K][n]
+ * u8 may be NULL.  done_k and prev are invsim_gae's, with its done0 and
+ * NULL-flag rules.  Per env, for k ascending:
+ *   if prev:   the NEXT_STEP reset row:  out[k][n] = +0.0;  valid = 0;  ret = +0.0
+ *   else:      t = ret * gamma;  ret = t + reward[k][n];  out[k][n] = ret;  valid = 1;
+ *              if done_k: ret = +0.0 after the store
+ * K < 0 or n_envs < 0 is INVSIM_EINVAL; K == 0 or n_envs == 0 returns INVSIM_OK
+ * without a launch; otherwise a NULL reward, ret or out is INVSIM_EINVAL.
+ *
+ * invsim_normalize_rewards: stats is the [3][1] statistics of the returns;
+ *   var = cnt == 0 ? 1.0 : M2 / cnt;  sd = sqrt(var + epsilon);  v = reward[i] / sd
+ *   out[i] = v < -clip ? -clip : (v > clip ? clip : v)          a NaN passes
+ * i.e. np.clip(reward / np.sqrt(var + eps), -clip, clip).  out may alias reward.
+ * clip <= 0 or NaN and count < 0 are INVSIM_EINVAL; count == 0 is a no-op;
+ * otherwise a NULL reward / stats / out is INVSIM_EINVAL.
+ *
+ * invsim_norm_params: var as above per column; inv = 1.0 / sqrt(var + epsilon);
+ * scale[c] = (float)inv;  shift[c] = (float)(-(mean * inv)): device f32 [cols],
+ * shift may be NULL.  fmaf(x, scale, shift) is then the "MLP actor" input stage.
+ * cols < 1 or a NULL stats / scale is INVSIM_EINVAL, cols > 1024 INVSIM_ERANGE.
+ *
+ * invsim_mlp_set_input_norm writes the object's in_scale / in_shift rows from
+ * device f32 [obs_dim] arrays: one small launch on `stream`, with
+ * invsim_mlp_update's ordering and capture rules (launches on `stream` after it
+ * see the new rows; a replay re-reads the arrays).  Actors and value objects
+ * alike.  INVSIM_EINVAL: an object created without in_scale (it has no such
+ * rows), another handle's object, a NULL array. */
+#define INVSIM_DTYPE_I64 0
+#define INVSIM_DTYPE_F32 1
+#define INVSIM_DTYPE_F64 2
+#define INVSIM_MOMENTS_BLOCK 64     /* rows per leaf of invsim_moments' tree */
+int invsim_moments_scratch_bytes(int64_t rows, int32_t cols, int64_t *bytes);
+int invsim_moments(const void *x /* [rows][cols] */, int32_t dtype, int64_t rows, int32_t cols,
+                   const uint8_t *mask /* [rows] or NULL */, double *stats /* [3][cols], in/out */,
+                   void *scratch, int64_t scratch_bytes, void *stream);
+int invsim_discounted_returns(const double *reward /* [K][n] */, const uint8_t *terminated, const uint8_t *truncated /* [K][n], either may be NULL */,
+                              const uint8_t *done0 /* [n] or NULL */, int32_t K, int64_t n_envs, double gamma,
+                              double *ret /* [n], in/out */, double *out /* [K][n] */, uint8_t *valid /* [K][n], may be NULL */,
+                              void *stream);
+int invsim_normalize_rewards(const double *reward /* [count] */, int64_t count, const double *stats /* [3][1] */,
+                             double epsilon, double clip, double *out /* [count], may alias reward */, void *stream);
+int invsim_norm_params(const double *stats /* [3][cols] */, int32_t cols, double epsilon, float *scale /* [cols] */,
+                       float *shift /* [cols], may be NULL */, void *stream);
+int invsim_mlp_set_input_norm(invsim_handle *h, invsim_mlp *m, const float *scale, const float *shift /* DEVICE [obs_dim] */,
+                              void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

@@ -16,6 +16,7 @@
 #include "launch.hpp"
 #include "gae.hpp"
 #include "mlp_policy.hpp"
+#include "norm.hpp"
 
 using namespace invsim;
 
@@ -1663,6 +1664,80 @@ int invsim_gae(const double *reward, const uint8_t *terminated, const uint8_t *t
     hipError_t e = gae_launch(reward, terminated, truncated, done0, value0, values, K, n_envs, gamma, lambda, advantages,
                               returns, valid, (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "gae launch");
+}
+
+// ------------------------------------------------------------------ running normalisation
+static int moments_shape_check(int64_t rows, int32_t cols) {
+    if (rows < 0 || cols < 1) return fail(nullptr, INVSIM_EINVAL, "moments: rows must be >= 0 and cols >= 1");
+    if (cols > 1024) return fail(nullptr, INVSIM_ERANGE, "moments: at most 1024 columns");
+    return INVSIM_OK;
+}
+
+int invsim_moments_scratch_bytes(int64_t rows, int32_t cols, int64_t *bytes) {
+    if (!bytes) return fail(nullptr, INVSIM_EINVAL, "null argument");
+    if (int rc = moments_shape_check(rows, cols)) return rc;
+    *bytes = moments_scratch_bytes(rows, cols);
+    return INVSIM_OK;
+}
+
+int invsim_moments(const void *x, int32_t dtype, int64_t rows, int32_t cols, const uint8_t *mask, double *stats,
+                   void *scratch, int64_t scratch_bytes, void *stream) {
+    TraceRange tr_("invsim_moments");
+    if (int rc = moments_shape_check(rows, cols)) return rc;
+    if (dtype != INVSIM_DTYPE_I64 && dtype != INVSIM_DTYPE_F32 && dtype != INVSIM_DTYPE_F64)
+        return fail(nullptr, INVSIM_EINVAL, "moments: dtype must be INVSIM_DTYPE_I64, _F32 or _F64");
+    if (rows == 0) return INVSIM_OK;
+    if (!x || !stats || !scratch) return fail(nullptr, INVSIM_EINVAL, "moments: null x / stats / scratch");
+    if (scratch_bytes < moments_scratch_bytes(rows, cols))
+        return fail(nullptr, INVSIM_ERANGE, "moments: scratch is smaller than invsim_moments_scratch_bytes");
+    hipError_t e = moments_launch(x, dtype, rows, cols, mask, stats, static_cast<double *>(scratch), (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "moments launch");
+}
+
+int invsim_discounted_returns(const double *reward, const uint8_t *terminated, const uint8_t *truncated,
+                              const uint8_t *done0, int32_t K, int64_t n_envs, double gamma, double *ret, double *out,
+                              uint8_t *valid, void *stream) {
+    TraceRange tr_("invsim_discounted_returns");
+    if (K < 0 || n_envs < 0) return fail(nullptr, INVSIM_EINVAL, "discounted_returns: negative size");
+    if (K == 0 || n_envs == 0) return INVSIM_OK;
+    if (!reward || !ret || !out) return fail(nullptr, INVSIM_EINVAL, "discounted_returns: null reward / ret / out");
+    hipError_t e = discounted_returns_launch(reward, terminated, truncated, done0, K, n_envs, gamma, ret, out, valid,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "discounted_returns launch");
+}
+
+int invsim_normalize_rewards(const double *reward, int64_t count, const double *stats, double epsilon, double clip,
+                             double *out, void *stream) {
+    TraceRange tr_("invsim_normalize_rewards");
+    if (!(clip > 0.0)) return fail(nullptr, INVSIM_EINVAL, "normalize_rewards: clip must be > 0");
+    if (count < 0) return fail(nullptr, INVSIM_EINVAL, "normalize_rewards: negative count");
+    if (count == 0) return INVSIM_OK;
+    if (!reward || !stats || !out) return fail(nullptr, INVSIM_EINVAL, "normalize_rewards: null reward / stats / out");
+    hipError_t e = normalize_rewards_launch(reward, count, stats, epsilon, clip, out, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "normalize_rewards launch");
+}
+
+int invsim_norm_params(const double *stats, int32_t cols, double epsilon, float *scale, float *shift, void *stream) {
+    TraceRange tr_("invsim_norm_params");
+    if (cols < 1) return fail(nullptr, INVSIM_EINVAL, "norm_params: cols must be >= 1");
+    if (cols > 1024) return fail(nullptr, INVSIM_ERANGE, "norm_params: at most 1024 columns");
+    if (!stats || !scale) return fail(nullptr, INVSIM_EINVAL, "norm_params: null stats / scale");
+    hipError_t e = norm_params_launch(stats, cols, epsilon, scale, shift, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(nullptr, e, "norm_params launch");
+}
+
+int invsim_mlp_set_input_norm(invsim_handle *h, invsim_mlp *m, const float *scale, const float *shift, void *stream) {
+    TraceRange tr_("invsim_mlp_set_input_norm");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (!m->dev.in_scale)
+        return fail(h, INVSIM_EINVAL, "this invsim_mlp was created without in_scale / in_shift: it has no input rows to write");
+    if (!scale || !shift) return fail(h, INVSIM_EINVAL, "null scale / shift");
+    DeviceGuard g(h->device);
+    // into m->blob, which is ours to write
+    hipError_t e = mlp_set_rows_launch(const_cast<float *>(m->dev.in_scale), const_cast<float *>(m->dev.in_shift), scale,
+                                       shift, m->dev.dims[0], (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp set_input_norm launch");
 }
 
 int invsim_set_episode_sink(invsim_handle *h, double *ret, double *part) {

@@ -33,6 +33,10 @@ _LAZY = {
     "collect_rollout": "policies",
     "ValueMLP": "policies",
     "gae": "policies",
+    "RunningMoments": "policies",
+    "Normalizer": "policies",
+    "discounted_returns": "policies",
+    "normalize_rewards": "policies",
     "LevelsAgent": "policies",
     "NetLevelsAgent": "policies",
     "evaluate_levels": "policies",

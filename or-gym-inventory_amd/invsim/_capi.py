@@ -35,8 +35,12 @@ EXPORTS = (
     "invsim_mlp_set_gaussian", "invsim_mlp_sample", "invsim_rollout_mlp_sample",
     "invsim_mlp_create_value", "invsim_mlp_values", "invsim_gae", "invsim_mlp_update",
     "invsim_set_policy_levels", "invsim_set_policy_net_levels",
+    "invsim_moments_scratch_bytes", "invsim_moments", "invsim_discounted_returns", "invsim_normalize_rewards",
+    "invsim_norm_params", "invsim_mlp_set_input_norm",
 )
 ABI_VERSION = 4
+DTYPE_I64, DTYPE_F32, DTYPE_F64 = 0, 1, 2       # INVSIM_DTYPE_*
+MOMENTS_MAX_COLS = 1024
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
 
 
@@ -151,6 +155,12 @@ def _declare(lib):
         "invsim_mlp_update": ([H, P, P, P, P, P, P], C.c_int),
         "invsim_set_policy_levels": ([H, P, P], C.c_int),
         "invsim_set_policy_net_levels": ([H, P, P], C.c_int),
+        "invsim_moments_scratch_bytes": ([I64, I32, P], C.c_int),
+        "invsim_moments": ([P, I32, I64, I32, P, P, P, I64, P], C.c_int),
+        "invsim_discounted_returns": ([P, P, P, P, I32, I64, C.c_double, P, P, P, P], C.c_int),
+        "invsim_normalize_rewards": ([P, I64, P, C.c_double, C.c_double, P, P], C.c_int),
+        "invsim_norm_params": ([P, I32, C.c_double, P, P, P], C.c_int),
+        "invsim_mlp_set_input_norm": ([H, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

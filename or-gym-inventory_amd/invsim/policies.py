@@ -599,9 +599,9 @@ class MLPPolicyAgent(_Agent):
         if hit is not None and hit[0] is env._h:
             return hit[1]
         if self._updated:
-            raise RuntimeError(f"{self.name}: update_from_module has replaced the parameters on the env it was called "
-                               "with, and this object's host arrays are the old ones: build a new agent from the "
-                               "module for another env")
+            raise RuntimeError(f"{self.name}: update_from_module / set_input_norm has replaced the parameters on the "
+                               "env it was called with, and this object's host arrays are the old ones: build a new "
+                               "agent from the module for another env")
         out_dim = 1 if self._value else env.action_dim
         if self.dims[0] != env.obs_dim or self.dims[-1] != out_dim:
             raise ValueError(f"the network maps {self.dims[0]} -> {self.dims[-1]}, the env needs "
@@ -673,6 +673,36 @@ class MLPPolicyAgent(_Agent):
         _capi.check(env._lib.invsim_mlp_update(env._h, obj, C.cast(W, C.c_void_p), C.cast(B, C.c_void_p), p(sd), p(ls),
                                                env._stream()), env._h, "mlp_update")
         self._live = (ws, bs, sd, ls)
+        self._updated = True
+
+    def set_input_norm(self, env, scale, shift):
+        """Write new ``in_scale`` / ``in_shift`` rows into this network's device
+        copy on ``env`` from device tensors (``invsim_mlp_set_input_norm``): one
+        small launch on the env's stream, no allocation, no synchronisation,
+        legal under ``env.capture``.  ``scale`` / ``shift``: float32 contiguous
+        ``[obs_dim]`` tensors (``RunningMoments.scale_shift``'s); anything else is
+        a TypeError / ValueError before any library call, as is a network built
+        without ``in_scale`` (it has no such rows: give it any pair at
+        construction, e.g. ones and zeros).  The tensors stay referenced until
+        the next call.  As after ``update_from_module``, this object's host
+        arrays are not refreshed: afterwards it serves ``env`` only."""
+        if self.in_scale is None:
+            raise ValueError(f"{self.name}: built without in_scale / in_shift, so its device copy has no input rows to "
+                             "write; construct it with a pair (ones and zeros leave the input as it is)")
+        O = self.dims[0]
+        for t, what in ((scale, "scale"), (shift, "shift")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what} must be a torch tensor on the env's device, got {type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{what} must be float32, got {t.dtype}")
+            if tuple(t.shape) != (O,) or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {(O,)}, got {tuple(t.shape)}")
+        if scale.device != env.device or shift.device != env.device:
+            raise ValueError(f"scale / shift must be on {env.device}")
+        obj = self.device_object(env)
+        _capi.check(env._lib.invsim_mlp_set_input_norm(env._h, obj, scale.data_ptr(), shift.data_ptr(), env._stream()),
+                    env._h, "mlp_set_input_norm")
+        self._live_norm = (scale, shift)
         self._updated = True
 
 
@@ -856,7 +886,204 @@ def gae(reward, terminated, truncated, value0, values, gamma=0.99, gae_lambda=0.
     return out
 
 
-def collect_rollout(env, agent, K, obs0, metrics=None, critic=None, gamma=0.99, gae_lambda=0.95, done0=None):
+_NORM_DTYPES = {torch.int64: _capi.DTYPE_I64, torch.float32: _capi.DTYPE_F32, torch.float64: _capi.DTYPE_F64}
+
+
+def _stream_or_current(dev, stream):
+    return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+
+
+def _norm_flag(t, shape, what, dev):
+    if t is None:
+        return None
+    t = torch.as_tensor(t, device=dev)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return (t if t.dtype in (torch.bool, torch.uint8) else t != 0).contiguous()
+
+
+class RunningMoments:
+    """Running per-column count, mean and M2 (sum of squared deviations) on the
+    device, float64 ``[3, cols]`` in ``stats``, advanced by ``invsim_moments``:
+    a fixed binary tree of Chan merges over leaves of 64 rows, stated op by op
+    in ``include/invsim.h`` ("Running normalisation") and restated in
+    ``tests/norm_model.py``, so the statistics are defined bit for bit and do
+    not depend on scheduling.  It starts as SB3's ``RunningMeanStd``: count
+    1e-4, mean 0, variance 1 (M2 = 1e-4).
+
+    ``update(x, mask=None)`` folds the rows of ``x`` in: ``x`` is ``[..., cols]``
+    (any shape when ``cols == 1``), int64 / float32 / float64, on the device;
+    ``mask`` (bool / uint8, one entry per row) leaves rows out.  It reads ``x``
+    once, allocates nothing once its scratch is large enough (the scratch grows
+    on demand, which is refused during stream capture: run the largest shape
+    once before capturing), and never synchronises."""
+
+    def __init__(self, cols, device):
+        cols = int(cols)
+        if not 1 <= cols <= _capi.MOMENTS_MAX_COLS:
+            raise ValueError(f"cols must be 1..{_capi.MOMENTS_MAX_COLS}, got {cols}")
+        self.cols = cols
+        self.device = torch.device(device)
+        init = np.zeros((3, cols))
+        init[0] = init[2] = 1e-4
+        self.stats = torch.from_numpy(init).to(self.device)
+        self._scratch = None
+
+    def _rows(self, x, mask):
+        """validate; (x contiguous, mask uint8 / bool contiguous or None, rows)"""
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"x must be a torch tensor, got {type(x).__name__}")
+        if x.dtype not in _NORM_DTYPES:
+            raise TypeError(f"x must be int64, float32 or float64, got {x.dtype}")
+        if x.device != self.device:
+            raise ValueError(f"x must be on {self.device}, got {x.device}")
+        if self.cols > 1 and (x.dim() < 1 or x.shape[-1] != self.cols):
+            raise ValueError(f"x must have shape [..., {self.cols}], got {tuple(x.shape)}")
+        rows = x.numel() // self.cols
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device)
+            if mask.numel() != rows:
+                raise ValueError(f"mask must have one entry per row ({rows}), got shape {tuple(mask.shape)}")
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        return x.contiguous(), mask, rows
+
+    def update(self, x, mask=None, stream=None):
+        x, mask, rows = self._rows(x, mask)
+        if rows == 0:
+            return self
+        lib = _capi.lib()
+        need = C.c_int64()
+        _capi.check(lib.invsim_moments_scratch_bytes(rows, self.cols, C.byref(need)), None, "moments_scratch_bytes")
+        if self._scratch is None or self._scratch.numel() < need.value:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("RunningMoments: the scratch must grow, which allocates: update once with the "
+                                   "largest shape before capturing")
+            self._scratch = torch.empty(max(need.value, 8), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(lib.invsim_moments(x.data_ptr(), _NORM_DTYPES[x.dtype], rows, self.cols,
+                                           None if mask is None else mask.data_ptr(), self.stats.data_ptr(),
+                                           self._scratch.data_ptr(), self._scratch.numel(),
+                                           _stream_or_current(self.device, stream)), None, "invsim_moments")
+        return self
+
+    @property
+    def count(self):
+        return self.stats[0]
+
+    @property
+    def mean(self):
+        return self.stats[1]
+
+    @property
+    def var(self):
+        """M2 / count (float64 ``[cols]``, a torch operation on the current stream)"""
+        return self.stats[2] / self.stats[0]
+
+    def scale_shift(self, epsilon=1e-8, stream=None):
+        """``(scale, shift)``, new float32 ``[cols]`` device tensors with
+        ``x * scale + shift = (x - mean) / sqrt(var + epsilon)`` (``invsim_norm_params``)"""
+        scale = torch.empty(self.cols, dtype=torch.float32, device=self.device)
+        shift = torch.empty_like(scale)
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.lib().invsim_norm_params(self.stats.data_ptr(), self.cols, float(epsilon),
+                                                       scale.data_ptr(), shift.data_ptr(),
+                                                       _stream_or_current(self.device, stream)),
+                        None, "invsim_norm_params")
+        return scale, shift
+
+
+def discounted_returns(reward, terminated, truncated, ret, gamma=0.99, done0=None, stream=None):
+    """VecNormalize's running discounted return over K rows, one HIP launch
+    (``invsim_discounted_returns``): ``ret`` ``[n]`` float64 is advanced in place
+    (``ret = ret * gamma + reward``, reset to 0 after a done and on the NEXT_STEP
+    reset row that follows it).  ``reward`` [K, n] float64; flags and ``done0`` as
+    in ``gae``.  Returns ``(out, valid)``: the return after every row, float64
+    [K, n], and bool [K, n], False on reset rows."""
+    if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+        raise ValueError("reward must be a [K, n] tensor")
+    if reward.dtype != torch.float64:
+        raise TypeError(f"reward must be float64, got {reward.dtype}")
+    dev = reward.device
+    K, n = reward.shape
+    if (not isinstance(ret, torch.Tensor) or ret.dtype != torch.float64 or tuple(ret.shape) != (n,)
+            or not ret.is_contiguous()):
+        raise ValueError(f"ret must be a contiguous float64 tensor of shape {(n,)}: it is advanced in place")
+    te, tr = _norm_flag(terminated, (K, n), "terminated", dev), _norm_flag(truncated, (K, n), "truncated", dev)
+    d0 = _norm_flag(done0, (n,), "done0", dev)
+    reward = reward.contiguous()
+    out = torch.empty((K, n), dtype=torch.float64, device=dev)
+    valid = torch.empty((K, n), dtype=torch.bool, device=dev)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().invsim_discounted_returns(p(reward), p(te), p(tr), p(d0), int(K), int(n), float(gamma),
+                                                          p(ret), p(out), p(valid), _stream_or_current(dev, stream)),
+                    None, "invsim_discounted_returns")
+    return out, valid
+
+
+def normalize_rewards(reward, stats, epsilon=1e-8, clip=10.0, out=None, stream=None):
+    """``clip(reward / sqrt(var + epsilon), -clip, clip)`` with ``var`` from the
+    ``[3, 1]`` statistics of the discounted returns (``invsim_normalize_rewards``);
+    float64 in and out, ``out`` may be ``reward`` itself."""
+    if not isinstance(reward, torch.Tensor) or reward.dtype != torch.float64:
+        raise TypeError("reward must be a float64 tensor")
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != (3, 1):
+        raise ValueError("stats must be the float64 [3, 1] statistics of a RunningMoments(1, ...)")
+    if not float(clip) > 0:
+        raise ValueError(f"clip must be > 0, got {clip}")
+    reward = reward.contiguous()
+    if out is None:
+        out = torch.empty_like(reward)
+    elif out.dtype != torch.float64 or out.shape != reward.shape or not out.is_contiguous():
+        raise ValueError("out must be float64, contiguous and of reward's shape")
+    with torch.cuda.device(reward.device):
+        s = _stream_or_current(reward.device, stream)
+        _capi.check(_capi.lib().invsim_normalize_rewards(reward.data_ptr(), reward.numel(), stats.data_ptr(),
+                                                         float(epsilon), float(clip), out.data_ptr(), s),
+                    None, "invsim_normalize_rewards")
+    return out
+
+
+class Normalizer:
+    """What SB3's ``VecNormalize`` keeps for a PPO / A2C learner, on the device:
+    ``obs_rms`` (``RunningMoments`` of the observations), ``ret_rms`` (of the
+    discounted return), the running return ``ret`` ``[N]``, and the current
+    ``obs_scale`` / ``obs_shift`` (float32 ``[obs_dim]``: ``obs * scale + shift``
+    is the normalised observation, for the learner's torch forward pass).
+    ``collect_rollout(..., normalize=norm)`` advances it; ``observe(obs)`` folds
+    further rows in (the first reset's ``obs0``).
+
+    Differences from ``VecNormalize``: the statistics advance once per K-step
+    ``collect_rollout`` call, not once per step (a rollout runs under the rows
+    the call began with); there is no ``clip_obs`` (the network's fused input
+    stage has no clamp); advantage normalisation stays with the learner (SB3
+    does it per minibatch); reset rows (``valid`` False) do not enter the
+    return statistics."""
+
+    def __init__(self, env, gamma=0.99, epsilon=1e-8, clip_reward=10.0, norm_obs=True, norm_reward=True):
+        if not float(clip_reward) > 0:
+            raise ValueError(f"clip_reward must be > 0, got {clip_reward}")
+        self.gamma, self.epsilon, self.clip_reward = float(gamma), float(epsilon), float(clip_reward)
+        self.norm_obs, self.norm_reward = bool(norm_obs), bool(norm_reward)
+        self.device = env.device
+        self.obs_rms = RunningMoments(env.obs_dim, env.device)
+        self.ret_rms = RunningMoments(1, env.device)
+        self.ret = torch.zeros(env.num_envs, dtype=torch.float64, device=env.device)
+        self.obs_scale, self.obs_shift = self.obs_rms.scale_shift(self.epsilon)
+
+    def observe(self, obs, stream=None):
+        """fold observation rows ``[..., obs_dim]`` (the env's obs dtype) into ``obs_rms`` and refresh the rows"""
+        self.obs_rms.update(obs, stream=stream)
+        self.obs_scale, self.obs_shift = self.obs_rms.scale_shift(self.epsilon, stream=stream)
+        return self
+
+    def normalize_obs(self, obs):
+        """``obs`` as the network's input stage sees it: float32 ``fma(obs, scale, shift)`` in torch"""
+        return torch.addcmul(self.obs_shift, obs.to(torch.float32), self.obs_scale)
+
+
+def collect_rollout(env, agent, K, obs0, metrics=None, critic=None, gamma=0.99, gae_lambda=0.95, done0=None,
+                    normalize=None):
     """K steps of every env under a ``GaussianMLPPolicyAgent``, everything an
     on-policy rollout buffer stores, from one C call (two launches per step,
     no Python in the loop).  Returns device tensors: ``obs`` [K, N, O] (row k is
@@ -876,28 +1103,69 @@ def collect_rollout(env, agent, K, obs0, metrics=None, critic=None, gamma=0.99, 
     bool, the last row's terminated | truncated, which is the next call's
     ``done0`` (``None``: no env finished just before ``obs0``).  Rows with
     ``valid`` False are NEXT_STEP reset rows: mask them out of the loss.
-    Without a critic the call and its result are what they were."""
+    Without a critic the call and its result are what they were.
+
+    With ``normalize`` (a ``Normalizer``) the running statistics advance inside
+    the call, a handful of further launches and still no synchronisation, in
+    this order: the rollout runs under the actor's current input rows; the K obs
+    rows are folded into ``normalize.obs_rms``; the new scale / shift are
+    written into the actor and into a ``ValueMLP`` critic (both must have been
+    built with ``in_scale`` / ``in_shift``); the critic's values are computed
+    under the new rows (a callable critic gets the observations already
+    normalised); the running discounted return advances over the K rows and its
+    valid rows are folded into ``normalize.ret_rms``; ``reward_norm`` is the
+    clipped reward over the return's standard deviation; GAE runs on
+    ``reward_norm``.  New keys: ``reward_norm`` [K, N] float64 (``reward`` stays
+    raw), ``obs_scale`` / ``obs_shift`` [O] float32 (the rows just written), and
+    ``done`` also without a critic.  Unlike SB3's ``VecNormalize`` the
+    statistics advance once per call, not per step; there is no ``clip_obs``;
+    advantages are not normalised (SB3 does that per minibatch, in the
+    learner).  Without ``normalize`` the call, its launches and its result are
+    what they were."""
     if not isinstance(agent, GaussianMLPPolicyAgent):
         raise TypeError("collect_rollout needs a GaussianMLPPolicyAgent")
     K = int(K)
-    if critic is None:
+    if normalize is not None and not isinstance(normalize, Normalizer):
+        raise TypeError("normalize must be a Normalizer")
+    if critic is None and normalize is None:
         return _rollout_mlp_sample(env, agent, K, True, True, True, metrics, obs0, raw=True, log_prob=True)
-    if not isinstance(critic, ValueMLP) and not callable(critic):
+    if critic is not None and not isinstance(critic, ValueMLP) and not callable(critic):
         raise TypeError("critic must be a ValueMLP or a callable on the observations")
+    norm = normalize
+    if norm is not None and norm.norm_obs:
+        for net in (agent, critic) if isinstance(critic, ValueMLP) else (agent,):
+            if net.in_scale is None:
+                raise ValueError(f"{net.name}: normalize needs a network built with in_scale / in_shift")
     if obs0 is not None:
         obs0 = torch.as_tensor(obs0, device=env.device).to(env.obs_dtype).contiguous()
     out = _rollout_mlp_sample(env, agent, K, True, True, True, metrics, obs0, raw=True, log_prob=True)
-    N = env.num_envs
+    N, s = env.num_envs, env._stream()
+    if norm is not None and norm.norm_obs:
+        norm.obs_rms.update(out["obs"], stream=s)
+        norm.obs_scale, norm.obs_shift = norm.obs_rms.scale_shift(norm.epsilon, stream=s)
+        agent.set_input_norm(env, norm.obs_scale, norm.obs_shift)
+        if isinstance(critic, ValueMLP):
+            critic.set_input_norm(env, norm.obs_scale, norm.obs_shift)
     if isinstance(critic, ValueMLP):
         v = torch.empty((K + 1, N), dtype=torch.float32, device=env.device)
         env._mlp_values_into(critic, obs0, N, v[0])
         env._mlp_values_into(critic, out["obs"], K * N, v[1:])
-    else:
-        v = critic(torch.cat([obs0[None], out["obs"]]).float())
+    elif critic is not None:
+        allobs = torch.cat([obs0[None], out["obs"]])
+        v = critic(norm.normalize_obs(allobs) if norm is not None and norm.norm_obs else allobs.float())
         v = v.detach().reshape(K + 1, N).to(torch.float32).contiguous()
-    out.update(gae(out["reward"], out["terminated"], out["truncated"], v[0], v[1:], gamma, gae_lambda, done0,
-                   stream=env._stream()))
-    out["values"], out["last_value"] = v[:K], v[K]
+    reward = out["reward"]
+    if norm is not None:
+        if norm.norm_reward:
+            dr, dr_valid = discounted_returns(reward, out["terminated"], out["truncated"], norm.ret, norm.gamma, done0,
+                                              stream=s)
+            norm.ret_rms.update(dr, mask=dr_valid, stream=s)
+            reward = normalize_rewards(reward, norm.ret_rms.stats, norm.epsilon, norm.clip_reward, stream=s)
+        out["reward_norm"] = reward
+        out["obs_scale"], out["obs_shift"] = norm.obs_scale, norm.obs_shift
+    if critic is not None:
+        out.update(gae(reward, out["terminated"], out["truncated"], v[0], v[1:], gamma, gae_lambda, done0, stream=s))
+        out["values"], out["last_value"] = v[:K], v[K]
     out["done"] = (out["terminated"][K - 1] | out["truncated"][K - 1]) if K else torch.zeros(N, dtype=torch.bool,
                                                                                           device=env.device)
     return out
