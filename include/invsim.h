@@ -602,6 +602,104 @@ int invsim_norm_params(const double *stats /* [3][cols] */, int32_t cols, double
 int invsim_mlp_set_input_norm(invsim_handle *h, invsim_mlp *m, const float *scale, const float *shift /* DEVICE [obs_dim] */,
                               void *stream);
 
+/* ---- PPO gradients: the learner's half of an on-policy iteration for the
+ * in-library actor and critic (separate networks, a state-independent log_std):
+ * SB3's PPO.train loss and its gradient with respect to every weight, bias and
+ * log_std, over one minibatch of a collected rollout.  The optimiser stays with
+ * the caller: the gradients land in device arrays of torch's layouts, and
+ * invsim_mlp_update hands the new weights back.
+ *
+ * Sample space.  A call addresses samples s = 0 .. S - 1.  Sample s reads
+ * observation row s of the virtual concatenation of obs0 [n0][O] and obs [.][O]
+ * (obs dtype): row s is s < n0 ? obs0[s] : obs[s - n0].  With n0 = N, obs0 the
+ * rollout's first input and obs its [K][N][O] block, sample k * N + n gets the
+ * observation the network saw at step k; no copy and no cast is made.  The
+ * kernel casts as the "MLP actor" `input` stage does, in_scale / in_shift as
+ * they are in the object's blob when the launch runs.  raw_actions [S][A],
+ * old_logp [S], advantages [S], returns [S] and valid [S] (u8, or NULL: every
+ * sample counts) are indexed by s.  idx (device int64 [rows], or NULL: 0 ..
+ * rows - 1) names the minibatch's samples; repeats are allowed.  The caller
+ * answers for 0 <= idx[r] < S: nothing is written through idx.
+ *
+ * Loss, over the minibatch's valid samples (valid[s] != 0), n their count,
+ * every mean a sum divided by n; a minibatch with n = 0 writes all-zero
+ * gradients and stats:
+ *   forward    mean [A] (actor) and v (critic) are the "MLP actor" contract
+ *              through `output`, out_activation and out_scale / out_shift included
+ *   sample     z_a = (raw_a - mean_a) / std_a
+ *   log-prob   logp = logp0 - sum_a (0.5 z_a^2 + log_std_a), logp0 the
+ *              "Gaussian MLP actor" constant
+ *   ratio      ratio = exp(logp - old_logp)
+ *   advantage  with adv_stats (device f64 [3]: count, mean, M2, the layout of
+ *              invsim_moments with one column): adv = (advantages[s] - mean) /
+ *              (sqrt(M2 / (count - 1)) + 1e-8); a count below 2 leaves the
+ *              advantage as it is.  Without: adv = advantages[s]
+ *   policy     policy_loss = -mean(min(adv * ratio, adv * clamp(ratio, 1 -
+ *              clip_range, 1 + clip_range)))
+ *   entropy    entropy = sum_a (0.5 + 0.5 log(2 pi) + log_std_a)
+ *   actor      policy_loss - ent_coef * entropy
+ *   critic     vf_coef * mean((returns - v)^2)
+ * The outputs are the gradients of the actor loss (invsim_ppo_actor_grad) and
+ * of the critic loss (invsim_value_grad) with respect to every weight, bias
+ * and log_std.  std = exp(log_std) is treated as tied: d logp / d log_std_a =
+ * z_a^2 - 1.  tanh' is 1 - y^2 on the stored activation, relu' is y > 0; the
+ * derivative of a TANH output activation and the factor out_scale are
+ * included.  The clipped branch, where it is the smaller, has no gradient.
+ * A2C is the same call with clip_range = +inf and old_logp the current
+ * log-density.
+ *   actor stats   f64 [6]: n, policy_loss, entropy, approx_kl = mean((ratio - 1)
+ *                 - log ratio), clip fraction = mean(ratio outside [1 -
+ *                 clip_range, 1 + clip_range]), mean ratio
+ *   critic stats  f64 [2]: n, the unscaled mean((returns - v)^2)
+ *
+ * Rules.  A sample with valid[s] == 0 is selected out, not multiplied by zero:
+ * NaN or garbage in its rows reaches no output.  No atomics: the same call on
+ * the same inputs gives the same bits.  The forward half keeps the "MLP actor"
+ * contract op by op; how the backward half's partial sums are grouped (64
+ * samples in sequence per tile, tiles per workgroup, then at most
+ * INVSIM_PPO_MAX_GROUPS partials per parameter in f64) is the implementation's,
+ * so gradients are defined to a tolerance, not op by op.  Outputs are
+ * overwritten, not accumulated.  grad_weight / grad_bias are host arrays of
+ * n_layers DEVICE pointers in torch's layouts ([dims[l+1]][dims[l]] /
+ * [dims[l+1]]); the arrays or an entry may be NULL (that gradient is not
+ * written), as may grad_log_std [A] and stats.  The calls make no allocation
+ * and no synchronisation and are legal inside a capture bracket; they read the
+ * object's blob when they run, so a replay after invsim_mlp_update follows the
+ * new weights.  scratch is caller-owned device memory of at least
+ * invsim_ppo_scratch_bytes bytes, 8-byte aligned; the call may overwrite all of
+ * it.  Two launches per call: min(ceil(rows / 64), INVSIM_PPO_MAX_GROUPS)
+ * workgroups, then the reduction of their partial sums.
+ *
+ * Refusals are decided on the host before any launch.  INVSIM_EINVAL: a value
+ * object given to invsim_ppo_actor_grad or an actor to invsim_value_grad; an
+ * actor without a Gaussian; another handle's object; rows < 0 or n0 < 0;
+ * clip_range <= 0 or NaN; then, unless rows == 0 (a no-op returning INVSIM_OK):
+ * a NULL obs, a NULL obs0 with n0 > 0, NULL raw_actions / old_logp / advantages
+ * / returns, a NULL scratch.  INVSIM_ERANGE: scratch_bytes below the
+ * requirement, and a network whose activations of one tile do not fit the LDS:
+ *   (dims[0] + ... + dims[n_layers] + dims[n_layers]) * 260 > 163840
+ * (every layer's 64 activations at a row stride of 65 floats, and the rescaled
+ * output beside the last layer's).  33-256-256-3 and 68-256-256-11 fit; not
+ * every legal invsim_mlp does.  invsim_ppo_scratch_bytes is handle-free and
+ * host only: INVSIM_EINVAL for NULL dims, n_layers outside
+ * 1..INVSIM_MLP_MAX_LAYERS, a width outside what invsim_mlp_create accepts or
+ * rows < 0, INVSIM_ERANGE by the same inequality; its value is monotone in
+ * rows. */
+#define INVSIM_PPO_MAX_GROUPS 256   /* workgroups of one gradient launch: the number of partial sums */
+int invsim_ppo_scratch_bytes(const int32_t *dims /* host [n_layers + 1] */, int32_t n_layers, int64_t rows, int64_t *bytes);
+int invsim_ppo_actor_grad(invsim_handle *h, const invsim_mlp *m, const void *obs0 /* [n0][O] */, int64_t n0,
+                          const void *obs /* [.][O] */, const int64_t *idx /* [rows] or NULL */, int64_t rows,
+                          const uint8_t *valid /* [S] or NULL */, const float *raw_actions /* [S][A] */,
+                          const float *old_logp /* [S] */, const float *advantages /* [S] */,
+                          const double *adv_stats /* [3] or NULL */, double clip_range, double ent_coef,
+                          float *const *grad_weight, float *const *grad_bias, float *grad_log_std /* [A] or NULL */,
+                          double *stats /* [6] or NULL */, void *scratch, int64_t scratch_bytes, void *stream);
+int invsim_value_grad(invsim_handle *h, const invsim_mlp *m, const void *obs0 /* [n0][O] */, int64_t n0,
+                      const void *obs /* [.][O] */, const int64_t *idx /* [rows] or NULL */, int64_t rows,
+                      const uint8_t *valid /* [S] or NULL */, const float *returns /* [S] */, double vf_coef,
+                      float *const *grad_weight, float *const *grad_bias, double *stats /* [2] or NULL */,
+                      void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- RandomAgent (INVSIM_POLICY_RANDOM).  The reference never seeds
  * action_space, so its RandomAgent has no trajectory to match; the contract is
  * numpy's Generator on a stream of the env's own:

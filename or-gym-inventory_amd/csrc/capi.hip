@@ -17,6 +17,7 @@
 #include "gae.hpp"
 #include "mlp_policy.hpp"
 #include "norm.hpp"
+#include "ppo_grad.hpp"
 
 using namespace invsim;
 
@@ -1330,6 +1331,7 @@ static int mlp_create(invsim_handle *h, const invsim_mlp_spec *sp, invsim_mlp **
     const size_t esz = i64 ? 8 : 4;
     const size_t n_el = (size_t)std::max<int64_t>(h->N, 1);
     hipError_t e = mlp_prepare();
+    if (e == hipSuccess) e = ppo_prepare();
     if (e == hipSuccess) e = hipMalloc(&m->blob, blob.size() * sizeof(float));
     if (!value) {        // the closed loop's scratch rows: a value network is never in that loop
         if (e == hipSuccess) e = hipMalloc(&m->obs_row, n_el * O * esz);
@@ -1738,6 +1740,108 @@ int invsim_mlp_set_input_norm(invsim_handle *h, invsim_mlp *m, const float *scal
     hipError_t e = mlp_set_rows_launch(const_cast<float *>(m->dev.in_scale), const_cast<float *>(m->dev.in_shift), scale,
                                        shift, m->dev.dims[0], (hipStream_t)stream);
     return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "mlp set_input_norm launch");
+}
+
+// ------------------------------------------------------------------ PPO gradients
+static int ppo_dims_check(invsim_handle *h, const int32_t *dims, int32_t n_layers) {
+    if (!dims || n_layers < 1 || n_layers > INVSIM_MLP_MAX_LAYERS)
+        return fail(h, INVSIM_EINVAL, "ppo: dims must hold n_layers + 1 widths, n_layers in 1.." + std::to_string(INVSIM_MLP_MAX_LAYERS));
+    for (int l = 0; l <= n_layers; l++)
+        if (dims[l] < 1 || dims[l] > (l == n_layers ? INVSIM_POLICY_MAX_ACTION : INVSIM_MLP_MAX_WIDTH))
+            return fail(h, INVSIM_EINVAL, "ppo: a width outside what invsim_mlp_create accepts");
+    if (ppo_lds_bytes(dims, n_layers) > PPO_LDS_MAX)
+        return fail(h, INVSIM_ERANGE, "ppo: the activations of one 64-sample tile, (sum of dims + dims[n_layers]) * 260 B, "
+                                      "exceed the 160 KiB of LDS");
+    return INVSIM_OK;
+}
+
+int invsim_ppo_scratch_bytes(const int32_t *dims, int32_t n_layers, int64_t rows, int64_t *bytes) {
+    if (!bytes) return fail(nullptr, INVSIM_EINVAL, "null argument");
+    if (rows < 0) return fail(nullptr, INVSIM_EINVAL, "ppo: rows must be >= 0");
+    if (int rc = ppo_dims_check(nullptr, dims, n_layers)) return rc;
+    *bytes = ppo_scratch_bytes(dims, n_layers, rows);
+    return INVSIM_OK;
+}
+
+// what the two gradient calls share: the object's shapes, the scratch layout and the output pointers
+static int ppo_common(invsim_handle *h, const invsim_mlp *m, const void *obs0, int64_t n0, const void *obs, const int64_t *idx,
+                      int64_t rows, const uint8_t *valid, float *const *gw, float *const *gb, double *stats, void *scratch,
+                      int64_t scratch_bytes, PpoArgs &a) {
+    const MlpDev &d = m->dev;
+    if (rows < 0 || n0 < 0) return fail(h, INVSIM_EINVAL, "ppo: rows and n0 must be >= 0");
+    if (int rc = ppo_dims_check(h, d.dims, d.n_layers)) return rc;
+    if (rows == 0) return INVSIM_OK;
+    if ((n0 > 0 && !obs0) || !obs) return fail(h, INVSIM_EINVAL, "ppo: null obs0 / obs");
+    if (!scratch) return fail(h, INVSIM_EINVAL, "ppo: null scratch");
+    if (scratch_bytes < ppo_scratch_bytes(d.dims, d.n_layers, rows))
+        return fail(h, INVSIM_ERANGE, "ppo: scratch is smaller than invsim_ppo_scratch_bytes");
+    a.dev = m->dev_copy;
+    a.obs0 = obs0, a.obs = obs, a.n0 = n0, a.rows = rows, a.idx = idx, a.valid = valid;
+    a.groups = ppo_groups(rows);
+    a.pfloats = ppo_partial_floats(d.dims, d.n_layers);
+    a.stat_part = static_cast<double *>(scratch);
+    a.part = reinterpret_cast<float *>(a.stat_part + (int64_t)a.groups * PPO_STATS);
+    a.n_layers = d.n_layers, a.A = d.dims[d.n_layers];
+    int64_t off = 0;
+    for (int l = 0; l < d.n_layers; l++) {
+        a.in[l] = d.dims[l], a.out[l] = d.dims[l + 1];
+        a.off[l] = off;
+        off += ((int64_t)d.dims[l] + 1) * d.dims[l + 1];
+        a.gw[l] = gw ? gw[l] : nullptr;
+        a.gb[l] = gb ? gb[l] : nullptr;
+    }
+    a.off[d.n_layers] = off;
+    a.stats = stats;
+    return INVSIM_OK;
+}
+
+int invsim_ppo_actor_grad(invsim_handle *h, const invsim_mlp *m, const void *obs0, int64_t n0, const void *obs,
+                          const int64_t *idx, int64_t rows, const uint8_t *valid, const float *raw_actions,
+                          const float *old_logp, const float *advantages, const double *adv_stats, double clip_range,
+                          double ent_coef, float *const *grad_weight, float *const *grad_bias, float *grad_log_std,
+                          double *stats, void *scratch, int64_t scratch_bytes, void *stream) {
+    TraceRange tr_("invsim_ppo_actor_grad");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (int rc = mlp_actor_check(h, m)) return rc;
+    if (!m->gauss)
+        return fail(h, INVSIM_EINVAL, "no Gaussian set on this invsim_mlp: give std and log_std with "
+                                      "invsim_mlp_set_gaussian or invsim_mlp_update");
+    if (!(clip_range > 0.0)) return fail(h, INVSIM_EINVAL, "ppo: clip_range must be > 0");
+    PpoArgs a{};
+    if (int rc = ppo_common(h, m, obs0, n0, obs, idx, rows, valid, grad_weight, grad_bias, stats, scratch, scratch_bytes, a))
+        return rc;
+    if (rows == 0) return INVSIM_OK;
+    if (!raw_actions || !old_logp || !advantages) return fail(h, INVSIM_EINVAL, "ppo: null raw_actions / old_logp / advantages");
+    a.raw = raw_actions, a.old_logp = old_logp, a.adv = advantages, a.adv_stats = adv_stats;
+    a.std = m->g_std, a.log_std = m->g_log_std, a.logp0 = m->logp0;
+    a.clip_lo = (float)(1.0 - clip_range), a.clip_hi = (float)(1.0 + clip_range);
+    a.gls = grad_log_std;
+    a.scale = 1.0, a.ent_coef = ent_coef;
+    DeviceGuard g(h->device);
+    hipError_t e = ppo_grad_launch(m->dev, a, h->family == INVSIM_INVMGMT, false, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "ppo actor gradient launch");
+}
+
+int invsim_value_grad(invsim_handle *h, const invsim_mlp *m, const void *obs0, int64_t n0, const void *obs,
+                      const int64_t *idx, int64_t rows, const uint8_t *valid, const float *returns, double vf_coef,
+                      float *const *grad_weight, float *const *grad_bias, double *stats, void *scratch,
+                      int64_t scratch_bytes, void *stream) {
+    TraceRange tr_("invsim_value_grad");
+    if (!h || !m) return fail(h, INVSIM_EINVAL, "null argument");
+    if (m->owner != h) return fail(h, INVSIM_EINVAL, "this invsim_mlp was created for another handle");
+    if (!m->value)
+        return fail(h, INVSIM_EINVAL, "this invsim_mlp is an actor: its gradient comes from invsim_ppo_actor_grad");
+    PpoArgs a{};
+    if (int rc = ppo_common(h, m, obs0, n0, obs, idx, rows, valid, grad_weight, grad_bias, stats, scratch, scratch_bytes, a))
+        return rc;
+    if (rows == 0) return INVSIM_OK;
+    if (!returns) return fail(h, INVSIM_EINVAL, "ppo: null returns");
+    a.returns = returns;
+    a.log_std = nullptr;
+    a.scale = vf_coef, a.ent_coef = 0.0;
+    DeviceGuard g(h->device);
+    hipError_t e = ppo_grad_launch(m->dev, a, h->family == INVSIM_INVMGMT, true, (hipStream_t)stream);
+    return e == hipSuccess ? INVSIM_OK : hip_fail(h, e, "value gradient launch");
 }
 
 int invsim_set_episode_sink(invsim_handle *h, double *ret, double *part) {

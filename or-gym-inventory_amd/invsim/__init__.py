@@ -37,6 +37,10 @@ _LAZY = {
     "Normalizer": "policies",
     "discounted_returns": "policies",
     "normalize_rewards": "policies",
+    "ppo_actor_grad": "policies",
+    "value_grad": "policies",
+    "ppo_scratch_bytes": "policies",
+    "PPOLearner": "policies",
     "LevelsAgent": "policies",
     "NetLevelsAgent": "policies",
     "evaluate_levels": "policies",

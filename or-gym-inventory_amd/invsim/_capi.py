@@ -37,10 +37,12 @@ EXPORTS = (
     "invsim_set_policy_levels", "invsim_set_policy_net_levels",
     "invsim_moments_scratch_bytes", "invsim_moments", "invsim_discounted_returns", "invsim_normalize_rewards",
     "invsim_norm_params", "invsim_mlp_set_input_norm",
+    "invsim_ppo_scratch_bytes", "invsim_ppo_actor_grad", "invsim_value_grad",
 )
 ABI_VERSION = 4
 DTYPE_I64, DTYPE_F32, DTYPE_F64 = 0, 1, 2       # INVSIM_DTYPE_*
 MOMENTS_MAX_COLS = 1024
+PPO_MAX_GROUPS = 256                            # INVSIM_PPO_MAX_GROUPS
 DEMAND_STREAMS = {"numpy": 0, "philox": 1}
 
 
@@ -161,6 +163,10 @@ def _declare(lib):
         "invsim_normalize_rewards": ([P, I64, P, C.c_double, C.c_double, P, P], C.c_int),
         "invsim_norm_params": ([P, I32, C.c_double, P, P, P], C.c_int),
         "invsim_mlp_set_input_norm": ([H, P, P, P, P], C.c_int),
+        "invsim_ppo_scratch_bytes": ([P, I32, I64, P], C.c_int),
+        "invsim_ppo_actor_grad": ([H, P, P, I64, P, P, I64, P, P, P, P, P, C.c_double, C.c_double, P, P, P, P, P, I64, P],
+                                  C.c_int),
+        "invsim_value_grad": ([H, P, P, I64, P, P, I64, P, P, C.c_double, P, P, P, P, I64, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -1171,6 +1171,254 @@ def collect_rollout(env, agent, K, obs0, metrics=None, critic=None, gamma=0.99, 
     return out
 
 
+def ppo_scratch_bytes(dims, rows):
+    """``invsim_ppo_scratch_bytes``: the scratch one gradient call over ``rows``
+    samples needs for a network of widths ``dims`` (host only, no GPU)."""
+    d = np.ascontiguousarray(np.asarray(dims, dtype=np.int32))
+    need = C.c_int64()
+    _capi.check(_capi.lib().invsim_ppo_scratch_bytes(d.ctypes.data, len(d) - 1, int(rows), C.byref(need)), None,
+                "ppo_scratch_bytes")
+    return need.value
+
+
+def _ppo_tensor(t, what, dtypes, numel, dev):
+    """a device array of a gradient call: checked, never converted (no hidden copy of a rollout)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{what} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.device != dev:
+        raise ValueError(f"{what} must be on {dev}, got {t.device}")
+    if not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise ValueError(f"{what} must be contiguous" + (f" with {numel} elements" if numel is not None else "")
+                         + f", got shape {tuple(t.shape)}")
+    return t
+
+
+def _ppo_samples(env, net, buf, obs0, idx, keys):
+    """What the two gradient wrappers check before any library call.  Returns
+    (obs0 or None, n0, obs, idx or None, rows, valid or None, [buf[k] for k in keys])."""
+    if not isinstance(buf, dict):
+        raise TypeError("buf must be the dict collect_rollout(critic=...) returns")
+    for k in ("obs",) + tuple(keys):
+        if k not in buf:
+            raise ValueError(f"buf has no {k!r}: collect the rollout with critic=...")
+    dev, O = env.device, env.obs_dim
+    if net.dims[0] != O:
+        raise ValueError(f"{net.name} takes {net.dims[0]} inputs, the env's observations have {O}")
+    obs = _ppo_tensor(buf["obs"], "buf['obs']", (env.obs_dtype,), None, dev)
+    if obs.dim() < 2 or obs.shape[-1] != O:
+        raise ValueError(f"buf['obs'] must have shape [..., {O}], got {tuple(obs.shape)}")
+    n0 = 0
+    if obs0 is not None:
+        obs0 = _ppo_tensor(obs0, "obs0", (env.obs_dtype,), None, dev)
+        if obs0.dim() != 2 or obs0.shape[1] != O:
+            raise ValueError(f"obs0 must have shape [n0, {O}], got {tuple(obs0.shape)}")
+        n0 = obs0.shape[0]
+    S = obs.numel() // O          # samples: the first S rows of cat([obs0, obs])
+    per = [_ppo_tensor(buf[k], f"buf[{k!r}]", (torch.float32,), S * (net.dims[-1] if k == "raw_actions" else 1), dev)
+           for k in keys]
+    valid = buf.get("valid")
+    if valid is not None:
+        valid = _ppo_tensor(valid, "buf['valid']", (torch.bool, torch.uint8), S, dev)
+    rows = S
+    if idx is not None:
+        idx = _ppo_tensor(idx, "idx", (torch.int64,), None, dev)
+        if idx.dim() != 1:
+            raise ValueError(f"idx must be one-dimensional, got shape {tuple(idx.shape)}")
+        rows = idx.shape[0]
+    return obs0, n0, obs, idx, rows, valid, per
+
+
+class _PPOGrads:
+    """Gradient tensors of one network in torch's layouts, the pointer arrays a
+    gradient call takes, and a scratch that grows on demand (not during capture)."""
+
+    def __init__(self, net, dev, log_std=False):
+        self.dims = list(net.dims)
+        self.weight = [torch.zeros(w.shape, dtype=torch.float32, device=dev) for w in net.weights]
+        self.bias = [torch.zeros(w.shape[0], dtype=torch.float32, device=dev) for w in net.weights]
+        self.log_std = torch.zeros(net.dims[-1], dtype=torch.float32, device=dev) if log_std else None
+        self.stats = torch.zeros(6 if log_std else 2, dtype=torch.float64, device=dev)
+        n = len(self.weight)
+        self.W = (C.c_void_p * n)(*[t.data_ptr() for t in self.weight])
+        self.B = (C.c_void_p * n)(*[t.data_ptr() for t in self.bias])
+        self.scratch = None
+
+    def scratch_for(self, rows, dev):
+        need = ppo_scratch_bytes(self.dims, rows)
+        if self.scratch is None or self.scratch.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the gradient scratch must grow, which allocates: call once with the largest "
+                                   "minibatch before capturing")
+            self.scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        return self.scratch
+
+    def result(self):
+        out = {"weight": self.weight, "bias": self.bias, "stats": self.stats}
+        if self.log_std is not None:
+            out["log_std"] = self.log_std
+        return out
+
+
+def ppo_actor_grad(env, pi, buf, obs0, idx=None, clip_range=0.2, ent_coef=0.0, adv_stats=None, out=None):
+    """The gradient of SB3's PPO actor loss over one minibatch of a collected
+    rollout, two HIP launches (``invsim_ppo_actor_grad``; ``include/invsim.h``
+    "PPO gradients" states the loss).  ``pi``: the ``GaussianMLPPolicyAgent`` the
+    rollout was collected with; ``buf``: ``collect_rollout(critic=...)``'s dict
+    (``obs``, ``raw_actions``, ``log_prob``, ``advantages`` and, if present,
+    ``valid`` are read in place, never copied or cast); ``obs0``: the rollout's
+    first input ``[N, O]``, so that sample ``k * N + n`` reads the observation
+    the network saw at step k (``None``: sample s reads ``obs`` row s).  ``idx``:
+    int64 device tensor of sample numbers, the minibatch (``None``: every
+    sample; the caller answers for its range).  ``adv_stats``: float64 ``[3]``
+    or ``[3, 1]`` (``RunningMoments(1).stats``) to normalise the advantages
+    with, or ``None``.  A2C: ``clip_range=float('inf')``.  Returns ``{"weight":
+    [...], "bias": [...], "log_std": t, "stats": t}``, float32 device tensors in
+    ``torch.nn.Linear``'s layouts and float64 ``[6]`` (n, policy loss, entropy,
+    approx_kl, clip fraction, mean ratio).  ``out``: an earlier result's holder
+    (``PPOLearner`` keeps one), else new tensors.  No synchronisation; legal
+    under ``env.capture`` once the scratch has its size."""
+    if not isinstance(pi, GaussianMLPPolicyAgent):
+        raise TypeError("ppo_actor_grad needs the GaussianMLPPolicyAgent the rollout was collected with")
+    if not float(clip_range) > 0:
+        raise ValueError(f"clip_range must be > 0, got {clip_range}")
+    obs0, n0, obs, idx, rows, valid, (raw, logp, adv) = _ppo_samples(env, pi, buf, obs0, idx,
+                                                                    ("raw_actions", "log_prob", "advantages"))
+    if adv_stats is not None:
+        if (not isinstance(adv_stats, torch.Tensor) or adv_stats.dtype != torch.float64 or adv_stats.numel() != 3
+                or not adv_stats.is_contiguous() or adv_stats.device != env.device):
+            raise ValueError("adv_stats must be a contiguous float64 device tensor of 3 entries (count, mean, M2)")
+    g = out if out is not None else _PPOGrads(pi, env.device, log_std=True)
+    obj = pi.device_object(env)
+    if rows == 0:
+        return g.result()
+    scratch = g.scratch_for(rows, env.device)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _capi.check(env._lib.invsim_ppo_actor_grad(
+        env._h, obj, p(obs0), n0, p(obs), p(idx), rows, p(valid), p(raw), p(logp), p(adv), p(adv_stats),
+        float(clip_range), float(ent_coef), C.cast(g.W, C.c_void_p), C.cast(g.B, C.c_void_p), p(g.log_std), p(g.stats),
+        scratch.data_ptr(), scratch.numel(), env._stream()), env._h, "ppo_actor_grad")
+    return g.result()
+
+
+def value_grad(env, vf, buf, obs0, idx=None, vf_coef=0.5, out=None):
+    """The gradient of ``vf_coef * mean((returns - V)^2)`` over one minibatch
+    (``invsim_value_grad``): ``vf`` the ``ValueMLP``, everything else as
+    ``ppo_actor_grad`` (``buf['returns']`` in place of the actor's arrays).
+    Returns ``{"weight": [...], "bias": [...], "stats": t}``, ``stats`` float64
+    ``[2]``: n and the unscaled mean squared error."""
+    if not isinstance(vf, ValueMLP):
+        raise TypeError("value_grad needs a ValueMLP")
+    obs0, n0, obs, idx, rows, valid, (ret,) = _ppo_samples(env, vf, buf, obs0, idx, ("returns",))
+    g = out if out is not None else _PPOGrads(vf, env.device)
+    obj = vf.device_object(env)
+    if rows == 0:
+        return g.result()
+    scratch = g.scratch_for(rows, env.device)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _capi.check(env._lib.invsim_value_grad(
+        env._h, obj, p(obs0), n0, p(obs), p(idx), rows, p(valid), p(ret), float(vf_coef), C.cast(g.W, C.c_void_p),
+        C.cast(g.B, C.c_void_p), p(g.stats), scratch.data_ptr(), scratch.numel(), env._stream()), env._h, "value_grad")
+    return g.result()
+
+
+class PPOLearner:
+    """SB3's ``PPO.train`` for the in-library actor and critic (separate
+    networks, state-independent ``log_std``): minibatch epochs whose forward,
+    loss and backward are the two gradient calls above, with the optimiser in
+    torch.  ``pi`` / ``vf``: the ``GaussianMLPPolicyAgent`` / ``ValueMLP`` the
+    rollouts are collected with; ``actor`` / ``critic``: the ``nn.Sequential``
+    modules they were built from (float32 parameters on the env's device);
+    ``log_std``: the ``nn.Parameter`` ``[A]``.  The learner owns preallocated
+    gradient tensors, which every parameter's ``.grad`` aliases from then on,
+    the scratch, and a ``RunningMoments(1)`` for the advantages.
+
+    ``update(buf, obs0)`` runs on the env's stream and never synchronises: the
+    advantage statistics over the rollout's valid rows (``invsim_moments``, once
+    per call); per epoch a device ``randperm``; per minibatch the two gradient
+    calls, ``clip_grad_norm_`` over actor, critic and ``log_std`` jointly,
+    ``optimizer.step()`` (default ``Adam(lr=3e-4, eps=1e-5, fused=True)``) and
+    ``update_from_module`` on both networks.  It returns the per-minibatch
+    statistics stacked on the device: ``{"actor": [M, 6], "critic": [M, 2]}``.
+
+    Differences from SB3: the advantages are normalised with the statistics of
+    the whole rollout's valid rows, not of each minibatch; reset rows (``valid``
+    False) are in the permutation but selected out of every sum, so a minibatch
+    averages over its valid samples; there is no ``clip_range_vf`` and no
+    ``target_kl``."""
+
+    def __init__(self, env, pi, vf, actor, critic, log_std, optimizer=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
+                 max_grad_norm=0.5, n_epochs=10, batch_size=4096, normalize_advantage=True):
+        if not isinstance(pi, GaussianMLPPolicyAgent):
+            raise TypeError("pi must be a GaussianMLPPolicyAgent")
+        if not isinstance(vf, ValueMLP):
+            raise TypeError("vf must be a ValueMLP")
+        if not isinstance(actor, torch.nn.Module) or not isinstance(critic, torch.nn.Module):
+            raise TypeError("actor and critic must be the torch modules the networks were built from")
+        if not isinstance(log_std, torch.nn.Parameter):
+            raise TypeError("log_std must be a torch.nn.Parameter")
+        if optimizer is not None and not isinstance(optimizer, torch.optim.Optimizer):
+            raise TypeError("optimizer must be a torch.optim.Optimizer or None")
+        if not float(clip_range) > 0:
+            raise ValueError(f"clip_range must be > 0, got {clip_range}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be > 0 or None, got {max_grad_norm}")
+        if int(n_epochs) < 1 or int(batch_size) < 1:
+            raise ValueError("n_epochs and batch_size must be >= 1")
+        a_params, c_params = pi._module_params(actor), vf._module_params(critic)
+        if tuple(log_std.shape) != (pi.dims[-1],):
+            raise ValueError(f"log_std must have shape {(pi.dims[-1],)}, got {tuple(log_std.shape)}")
+        self.params = [t for w, b in a_params + c_params for t in (w, b) if t is not None] + [log_std]
+        for t in self.params:
+            if t.dtype != torch.float32 or t.device != env.device or not t.is_contiguous():
+                raise ValueError(f"every parameter must be float32, contiguous and on {env.device}: its .grad aliases a "
+                                 "tensor the gradient kernels write")
+        self.env, self.pi, self.vf, self.actor, self.critic, self.log_std = env, pi, vf, actor, critic, log_std
+        self.clip_range, self.ent_coef, self.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
+        self.normalize_advantage = bool(normalize_advantage)
+        self._ga, self._gc = _PPOGrads(pi, env.device, log_std=True), _PPOGrads(vf, env.device)
+        for g, params in ((self._ga, a_params), (self._gc, c_params)):
+            for l, (w, b) in enumerate(params):
+                w.grad = g.weight[l]
+                if b is not None:
+                    b.grad = g.bias[l]
+        log_std.grad = self._ga.log_std
+        self.optimizer = optimizer if optimizer is not None else torch.optim.Adam(self.params, lr=3e-4, eps=1e-5,
+                                                                                  fused=True)
+        self.adv_rms = RunningMoments(1, env.device)
+
+    def update(self, buf, obs0, perms=None):
+        """One ``PPO.train``: ``n_epochs`` passes over ``buf`` in minibatches of
+        ``batch_size`` (the last one of an epoch may be short).  ``perms``: the
+        epochs' sample orders as int64 device tensors, one per epoch (any
+        length), default a device ``randperm`` of all samples each."""
+        env = self.env
+        S = buf["obs"].numel() // env.obs_dim
+        stats = None
+        if self.normalize_advantage:
+            self.adv_rms.stats.zero_()      # this rollout's statistics alone
+            self.adv_rms.update(buf["advantages"], mask=buf.get("valid"), stream=env._stream())
+            stats = self.adv_rms.stats
+        a_stats, c_stats = [], []
+        for e in range(self.n_epochs):
+            perm = perms[e] if perms is not None else torch.randperm(S, device=env.device)
+            for lo in range(0, perm.shape[0], self.batch_size):
+                idx = perm[lo:lo + self.batch_size]
+                ppo_actor_grad(env, self.pi, buf, obs0, idx, self.clip_range, self.ent_coef, stats, out=self._ga)
+                value_grad(env, self.vf, buf, obs0, idx, self.vf_coef, out=self._gc)
+                if self.max_grad_norm is not None:
+                    torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm, foreach=True)
+                self.optimizer.step()
+                self.pi.update_from_module(env, self.actor, log_std=self.log_std)
+                self.vf.update_from_module(env, self.critic)
+                a_stats.append(self._ga.stats.clone())
+                c_stats.append(self._gc.stats.clone())
+        return {"actor": torch.stack(a_stats), "critic": torch.stack(c_stats)}
+
+
 def _rollout_mlp(env, agent, K, obs, rewards, actions, metrics, obs0):
     """The closed loop of an MLPPolicyAgent: one invsim_rollout_mlp call."""
     if obs0 is None:
