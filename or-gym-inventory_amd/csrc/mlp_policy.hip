@@ -1,14 +1,15 @@
 // In-library MLP actor: observations in, actions out, one launch
 // (include/invsim.h "MLP actor" states the arithmetic op by op; every
-// multiply-add below is an explicit fmaf and nothing else adds or multiplies).
+// multiply-add below and in mlp_forward.hpp, which holds the forward chunk, is
+// an explicit fmaf and nothing else adds or multiplies).
 //
 // Layout.  One workgroup = 64 envs x 4 waves (8 for wide networks:
 // mlp_threads); lane = env in every wave.  The
 // activations of a layer live in LDS as [unit][MLP_ROW] floats (lane reads of
 // one unit: 64 consecutive words), two buffers, one workgroup barrier per
 // layer.  A layer's output units are cut into chunks of 16 (then of 4 for the
-// last 1..15) and dealt to the waves round-robin; a wave keeps a chunk's
-// accumulators in VGPRs and walks the inputs in ascending order: read x[i]
+// last 1..15) and dealt to the waves round-robin; mlp_forward.hpp's chunk
+// keeps its accumulators in VGPRs and walks the inputs in ascending order: read x[i]
 // once from LDS, one FMA per owned unit, which is the contract's order for
 // every unit.  The weights of one input are contiguous over the units (the
 // device copy is transposed and zero padded to a multiple of 4), indexed by
@@ -21,61 +22,12 @@
 
 #include "../../include/invsim.h"
 #include "device_common.hpp"
+#include "mlp_forward.hpp"
 #include "mlp_policy.hpp"
 #include "numpy_normal.hpp"
 
 namespace invsim {
 namespace {
-
-// The parameter blob is written before a launch (at create, or by an earlier
-// mlp_update_kernel launch, whose stores are visible at this one's start) and
-// only read by the network kernels: pointers into it are taken in the constant
-// address space, so every
-// wave-uniform read of it (the argument block, weights, biases, output scales)
-// is a scalar load whatever the compiler can prove about aliasing.
-#define MLP_CONST __attribute__((address_space(4)))
-typedef const float MLP_CONST *mlp_cfloat;
-typedef const MlpDev MLP_CONST &mlp_cdev;
-template <typename T>
-__device__ __forceinline__ const T MLP_CONST *mlp_const(const T *p) {
-    return (const T MLP_CONST *)(uintptr_t)p;
-}
-
-__device__ __forceinline__ float mlp_activate(float v, int kind) {
-    if (kind == INVSIM_MLP_RELU) return v > 0.0f ? v : 0.0f;   // NaN -> +0.0f
-    if (kind == INVSIM_MLP_TANH) return tanhf(v);
-    return v;
-}
-
-// CH output units base .. base + CH - 1 of layer l for this wave's 64 envs
-template <int CH>
-__device__ __forceinline__ void mlp_chunk(mlp_cdev m, int l, int base, const float *xin, float *xout, int lane) {
-    const int in = m.dims[l], out = m.dims[l + 1], opad = m.opad[l];
-    const bool last = l == m.n_layers - 1;
-    mlp_cfloat w = mlp_const(m.wt[l]) + base;
-    mlp_cfloat b = mlp_const(m.bias[l]) + base;
-    mlp_cfloat osc = mlp_const(m.out_scale), osh = mlp_const(m.out_shift);
-    float acc[CH];
-#pragma unroll
-    for (int u = 0; u < CH; u++) acc[u] = b[u];
-    const float *x = xin + lane;
-#pragma unroll 4
-    for (int i = 0; i < in; i++, w += opad, x += MLP_ROW) {
-        const float xi = *x;
-#pragma unroll
-        for (int u = 0; u < CH; u++) acc[u] = __builtin_fmaf(w[u], xi, acc[u]);
-    }
-    const int kind = last ? m.out_act : m.act;
-    const bool scale = last && m.out_scale;
-#pragma unroll
-    for (int u = 0; u < CH; u++) {
-        if (base + u < out) {        // wave-uniform
-            float v = mlp_activate(acc[u], kind);
-            if (scale) v = __builtin_fmaf(v, osc[base + u], osh[base + u]);
-            xout[(base + u) * MLP_ROW + lane] = v;
-        }
-    }
-}
 
 // invsim.policies.convert_actions, f32 spaces
 __device__ __forceinline__ float mlp_convert(float r, float lo, float hi, bool clip) {
@@ -141,8 +93,8 @@ __global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restric
         const float *xin = mlp_lds + (l & 1) * half;
         float *xout = mlp_lds + ((l + 1) & 1) * half;
         for (int c = wave; c < n16 + n4; c += waves) {
-            if (c < n16) mlp_chunk<16>(m, l, 16 * c, xin, xout, lane);
-            else mlp_chunk<4>(m, l, 16 * n16 + 4 * (c - n16), xin, xout, lane);
+            if (c < n16) mlp_chunk<16, false>(m, l, 16 * c, xin, xout, nullptr, lane);
+            else mlp_chunk<4, false>(m, l, 16 * n16 + 4 * (c - n16), xin, xout, nullptr, lane);
         }
         __syncthreads();
     }
@@ -167,8 +119,7 @@ __global__ __launch_bounds__(512) void mlp_policy_kernel(const MlpDev *__restric
                 for (int a = 0; a < A; a++) {
                     const float zf = (float)np_standard_normal(g);
                     smp[a * MLP_ROW] = __builtin_fmaf(sd[a], zf, res[a * MLP_ROW + lane]);
-                    acc = __builtin_fmaf(-0.5f * zf, zf, acc);
-                    acc = acc - lsd[a];
+                    acc = mlp_logp_term(acc, zf, lsd[a]);
                 }
                 if (sm.logp) sm.logp[e] = acc;
                 rows.store_state(e, g);

@@ -10,7 +10,7 @@
 //             network's input stage does, into LDS as [input][MLP_ROW]; a sample
 //             that is masked or past `rows` gets zeros, so that nothing it holds
 //             can reach a sum
-//   forward   mlp_policy.hip's chunk: weights by scalar loads from the blob, one
+//   forward   mlp_forward.hpp's chunk: weights by scalar loads from the blob, one
 //             fmaf per unit per input in ascending order.  Every layer keeps a
 //             buffer of its own, and the last layer stores both its activation
 //             (the derivative needs it) and the rescaled output
@@ -35,28 +35,14 @@
 #include <type_traits>
 
 #include "../../include/invsim.h"
+#include "mlp_forward.hpp"
 #include "ppo_grad.hpp"
 
 namespace invsim {
 namespace {
 
-// wave-uniform reads of the parameter blob as scalar loads (mlp_policy.hip)
-#define PPO_CONST __attribute__((address_space(4)))
-typedef const float PPO_CONST *ppo_cfloat;
-typedef const MlpDev PPO_CONST &ppo_cdev;
-template <typename T>
-__device__ __forceinline__ const T PPO_CONST *ppo_const(const T *p) {
-    return (const T PPO_CONST *)(uintptr_t)p;
-}
-
 constexpr int PPO_JC = 8;     // output units of one dW work item
 constexpr int PPO_IC = 8;     // inputs of one dx chunk
-
-__device__ __forceinline__ float ppo_activate(float v, int kind) {
-    if (kind == INVSIM_MLP_RELU) return v > 0.0f ? v : 0.0f;
-    if (kind == INVSIM_MLP_TANH) return tanhf(v);
-    return v;
-}
 
 // d activation / d pre-activation from the stored activation y
 __device__ __forceinline__ float ppo_act_grad(float d, float y, int kind) {
@@ -65,41 +51,9 @@ __device__ __forceinline__ float ppo_act_grad(float d, float y, int kind) {
     return d;
 }
 
-// The forward chunk of mlp_policy.hip (same order, same fmaf), writing the
-// activation to xout and, on the last layer, the rescaled output to yout.
-template <int CH>
-__device__ __forceinline__ void ppo_fwd_chunk(ppo_cdev m, int l, int base, const float *xin, float *xout, float *yout,
-                                              int lane) {
-    const int in = m.dims[l], out = m.dims[l + 1], opad = m.opad[l];
-    const bool last = l == m.n_layers - 1;
-    ppo_cfloat w = ppo_const(m.wt[l]) + base;
-    ppo_cfloat b = ppo_const(m.bias[l]) + base;
-    ppo_cfloat osc = ppo_const(m.out_scale), osh = ppo_const(m.out_shift);
-    float acc[CH];
-#pragma unroll
-    for (int u = 0; u < CH; u++) acc[u] = b[u];
-    const float *x = xin + lane;
-#pragma unroll 4
-    for (int i = 0; i < in; i++, w += opad, x += MLP_ROW) {
-        const float xi = *x;
-#pragma unroll
-        for (int u = 0; u < CH; u++) acc[u] = __builtin_fmaf(w[u], xi, acc[u]);
-    }
-    const int kind = last ? m.out_act : m.act;
-    const bool scale = last && m.out_scale;
-#pragma unroll
-    for (int u = 0; u < CH; u++) {
-        if (base + u < out) {        // wave-uniform
-            const float v = ppo_activate(acc[u], kind);
-            xout[(base + u) * MLP_ROW + lane] = v;
-            if (last) yout[(base + u) * MLP_ROW + lane] = scale ? __builtin_fmaf(v, osc[base + u], osh[base + u]) : v;
-        }
-    }
-}
-
 template <bool I64, bool CRITIC>
 __global__ __launch_bounds__(512) void ppo_grad_kernel(PpoArgs a) {
-    ppo_cdev m = *ppo_const(a.dev);
+    mlp_cdev m = *mlp_const(a.dev);
     using Obs = typename std::conditional<I64, long long, float>::type;
     extern __shared__ float ppo_lds[];
     const int tid = threadIdx.x, lane = tid & 63, threads = blockDim.x;
@@ -151,8 +105,8 @@ __global__ __launch_bounds__(512) void ppo_grad_kernel(PpoArgs a) {
                 const int n16 = out >> 4, n4 = ((out & 15) + 3) >> 2;
                 float *xout = const_cast<float *>(xin) + m.dims[l] * MLP_ROW;
                 for (int c = wave; c < n16 + n4; c += waves) {
-                    if (c < n16) ppo_fwd_chunk<16>(m, l, 16 * c, xin, xout, OUT, lane);
-                    else ppo_fwd_chunk<4>(m, l, 16 * n16 + 4 * (c - n16), xin, xout, OUT, lane);
+                    if (c < n16) mlp_chunk<16, true>(m, l, 16 * c, xin, xout, OUT, lane);
+                    else mlp_chunk<4, true>(m, l, 16 * n16 + 4 * (c - n16), xin, xout, OUT, lane);
                 }
                 __syncthreads();
                 xin = xout;
@@ -170,7 +124,7 @@ __global__ __launch_bounds__(512) void ppo_grad_kernel(PpoArgs a) {
                 ok = !a.valid || a.valid[s] != 0;
             }
             float *y = Y + lane, *o = OUT + lane;
-            ppo_cfloat osc = ppo_const(m.out_scale);
+            mlp_cfloat osc = mlp_const(m.out_scale);
             if (!ok) {
                 for (int k = 0; k < A; k++) y[k * MLP_ROW] = 0.0f, o[k * MLP_ROW] = 0.0f;
             } else if constexpr (CRITIC) {
@@ -182,13 +136,12 @@ __global__ __launch_bounds__(512) void ppo_grad_kernel(PpoArgs a) {
                 y[0] = ppo_act_grad(d, y[0], m.out_act);
                 o[0] = 0.0f;
             } else {
-                ppo_cfloat sd = ppo_const(a.std), lsd = ppo_const(a.log_std);
+                mlp_cfloat sd = mlp_const(a.std), lsd = mlp_const(a.log_std);
                 const float *raw = a.raw + s * A;
                 float acc = a.logp0;
                 for (int k = 0; k < A; k++) {
                     const float z = (raw[k] - o[k * MLP_ROW]) / sd[k];
-                    acc = __builtin_fmaf(-0.5f * z, z, acc);
-                    acc = acc - lsd[k];
+                    acc = mlp_logp_term(acc, z, lsd[k]);
                 }
                 const float lr = acc - a.old_logp[s];
                 const float ratio = expf(lr);
@@ -271,9 +224,9 @@ __global__ __launch_bounds__(512) void ppo_grad_kernel(PpoArgs a) {
             for (int c = wave; c < nic; c += waves) {
                 const int i0 = c * PPO_IC;
                 const int ni = in - i0 < PPO_IC ? in - i0 : PPO_IC;
-                ppo_cfloat wrow[PPO_IC];
+                mlp_cfloat wrow[PPO_IC];
 #pragma unroll
-                for (int u = 0; u < PPO_IC; u++) wrow[u] = ppo_const(m.wt[l]) + (i0 + (u < ni ? u : ni - 1)) * opad;
+                for (int u = 0; u < PPO_IC; u++) wrow[u] = mlp_const(m.wt[l]) + (i0 + (u < ni ? u : ni - 1)) * opad;
                 float acc[PPO_IC];
 #pragma unroll
                 for (int u = 0; u < PPO_IC; u++) acc[u] = 0.0f;
